@@ -5,10 +5,16 @@ time (bin/test_table.jl:80) -- fp64, inputs resident in HBM.  Primary workload (
 target: "10M x 10M, ~1e8-nnz SuiteSparse-like matrix"): `fe`, a 2D finite-element operator
 (5-point stencil, 2 unknowns per node, 1.0e7 x 1.0e7, 1.0e8 stored values) in 1DVBC form.
 
-N = 1 (plain `python bench.py`): the primary line carries `roofline` (HIP events on the launching
-stream + the committed rocprofv3 / PMC summaries), `cpu_baseline` (the reference's SIMD CPU kernel,
-oracle/vbc_simd.c, on the host cores) and `parity` (the GPU y of the timed region against the CPU
-oracle, oracle/vbc_oracle.c, on the same full-size input).  Secondaries in the same line:
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it
+builds the matrix and its HBM layout, warms up, times the K products, writes the last product's y
+with `--dump-outputs DIR` (DIR/<name>.npy; a fixed seeded sample of an array above the size cap) and
+prints the line, whose `roofline` comes from the HIP events around the same timed region (+ the
+committed rocprofv3 / PMC summaries).  Everything else runs only with `--full`:
+
+N = 1 with `--full`: the primary line also carries `cpu_baseline` (the reference's SIMD CPU kernel,
+oracle/vbc_simd.c, on the host cores), `parity` (the GPU y of the timed region against the CPU
+oracle, oracle/vbc_oracle.c, on the same full-size input) and `device` (the GPU and its clocks).
+Secondaries in the same line:
 `fe3d` (irregular 3D stiffness stand-in, 1e7 rows / 1e8 nnz), `ns` (SURVEY §8d's uniform-random
 NS-1DVBC from the reference's own generator, costs.jl:63-83) and `c5` (2D VBC, 16 RHS, matrix cores).
 
@@ -16,12 +22,13 @@ N > 1 (torchrun, one process per GPU): STRONG scaling of ONE matrix.  Every rank
 matrix, keeps its byte-balanced stripe range (distributed.ShardedSparseMatrix1DVBC, the GPU grid
 replacing the reference's threaded stripe loop multiply_1DVBC.jl:169-177) and times K products of
 its shard; `value` = algorithmic bytes of the WHOLE matrix / the slowest rank's time.  B'x writes
-disjoint y slices, so the primary needs no collective; `e2e` adds the all_gather that replicates y
-(RCCL over xGMI), and the C3 secondary (ldoor stand-in) reports the same plus the forward product
-with its RCCL all_reduce of y.
+disjoint y slices, so the primary needs no collective; with `--full`, `e2e` adds the all_gather that
+replicates y (RCCL over xGMI), `parity` checks the gathered y, the C3 secondary (ldoor stand-in)
+reports the same plus the forward product with its RCCL all_reduce of y, and `abi_sharded` drives
+the same split through the C ABI from one process.
 
     python bench.py [--gpus N --steps K --warmup W --workload fe|fe3d|ns|ns-mixed|c5|ldoor|ct20stif
-                     --dtype f64|f32]
+                     --dtype f64|f32 --full --dump-outputs DIR]
 """
 import argparse
 import json
@@ -39,6 +46,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level
 MALL_BYTES = 256 << 20  # MI355X Infinity Cache (MALL)
 METRIC = "1DVBC SpMV effective GB/s (and GFLOP/s) vs HBM roofline, 1/2/4/8 GPU"
 PARITY_TOL = {np.dtype(np.float64): 1e-10, np.dtype(np.float32): 1e-5}  # normwise rel-err (BASELINE)
+DUMP_BUDGET = 48 << 20  # --dump-outputs: bytes of array data per run (all ranks together)
+DUMP_SEED = 0x5EED  # --dump-outputs: generator seed of the sample taken from a larger array
 
 WORKLOADS = {"ns": "NS-1DVBC-10Mx10M-1e8nnz-w4-uniform",
              "ns-mixed": "NS-1DVBC-mixed-w1..8-1e8nnz-uniform",
@@ -303,8 +312,32 @@ def box_info(device):
     return out
 
 
-def measure(args, workload, dtype, device, local, with_cpu, with_parity, steps=None):
-    """One single-GPU workload: build, warm up, time K products, optional CPU baseline + parity."""
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: write each device array of the timed path's last step as outdir/<name>.npy in its
+    own float eltype.  `budget` bytes are shared evenly; an array above its share is cut to a fixed
+    sample (sorted flat indices from a generator seeded with DUMP_SEED: the same elements in every run
+    and every build).  Returns what was written, for the result line."""
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        assert a.dtype in (np.float32, np.float64), a.dtype
+        keep = share // a.itemsize
+        entry = {"elements": int(a.size), "dtype": str(a.dtype), "sampled": bool(a.size > keep)}
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, keep, replace=False))
+            a = a[idx]
+            entry.update(kept=int(keep), seed=DUMP_SEED)
+        np.save(outdir / f"{name}.npy", np.ascontiguousarray(a))
+        info[name] = entry
+    return info
+
+
+def measure(args, workload, dtype, device, local, with_cpu, with_parity, steps=None, dump=""):
+    """One single-GPU workload: build, warm up, time K products, optional CPU baseline + parity;
+    dump: directory that receives the y of the last timed product."""
     import torch
 
     import sparsematrixvbcs_amd as V
@@ -383,6 +416,8 @@ def measure(args, workload, dtype, device, local, with_cpu, with_parity, steps=N
     if csc:
         out["roofline"]["bytes_csc_formula"] = bytes_launch
         out["csc_equivalent_GBs"] = round(bytes_launch * steps / elapsed / 1e9, 2)
+    if dump:
+        out["dump"] = dump_outputs(dump, {"y": y})
     if with_parity:
         out["parity"] = parity(B, x_host, y, k, cols=tuple(range(k)) if k > 1 else (0,), trans=trans)
     if with_cpu:
@@ -393,8 +428,9 @@ def measure(args, workload, dtype, device, local, with_cpu, with_parity, steps=N
     return out
 
 
-def measure_sharded(args, workload, dtype, world, rank, local, device, forward=False):
-    """Strong scaling: ONE matrix split by stripes over the ranks; kernel-only and end-to-end."""
+def measure_sharded(args, workload, dtype, world, rank, local, device, forward=False, dump=""):
+    """Strong scaling: ONE matrix split by stripes over the ranks; kernel-only and (--full) end-to-end.
+    dump: directory that receives every rank's y slice of the last timed product (y_rank<r>.npy)."""
     import torch
     import torch.distributed as dist
 
@@ -420,25 +456,29 @@ def measure_sharded(args, workload, dtype, world, rank, local, device, forward=F
     elapsed, kernel_ms, graphed = timed_products(lambda: S.local_mul_t(y_local, x), args.steps, device, stream,
                                                  world, graph=not args.eager)
 
-    # end-to-end: the product plus the all_gather that replicates y on every rank (RCCL over xGMI)
-    y_full = torch.empty(B.n, dtype=x.dtype, device=device)
+    dumped = dump_outputs(dump, {f"y_rank{rank}": y_local}, DUMP_BUDGET // world) if dump else None
+
+    # end-to-end (--full): the product plus the all_gather that replicates y on every rank (RCCL over xGMI)
+    y_full = torch.empty(B.n, dtype=x.dtype, device=device) if args.full else None
 
     def e2e():
         S.local_mul_t(y_local, x)
         S.gather(y_local, out=y_full)
 
     e2e_steps = max(5, args.steps // 5)
-    with torch.cuda.stream(stream):
-        e2e()
-    torch.cuda.synchronize(device)
-    dist.barrier()
-    t0 = time.perf_counter()
-    with torch.cuda.stream(stream):
-        for _ in range(e2e_steps):
+    e2e_elapsed = 0.0
+    if args.full:
+        with torch.cuda.stream(stream):
             e2e()
-    torch.cuda.synchronize(device)
-    e2e_elapsed = time.perf_counter() - t0
-    dist.barrier()
+        torch.cuda.synchronize(device)
+        dist.barrier()
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            for _ in range(e2e_steps):
+                e2e()
+        torch.cuda.synchronize(device)
+        e2e_elapsed = time.perf_counter() - t0
+        dist.barrier()
 
     par = sharded_parity(args, B, S, x_host, x, y_full, y_local, world, rank, local, device, stream) \
         if not args.no_parity else None
@@ -485,7 +525,8 @@ def measure_sharded(args, workload, dtype, world, rank, local, device, forward=F
         },
         "e2e": {"value": round(bytes_total * e2e_steps / e2e_elapsed / 1e9, 2), "unit": "GB/s",
                 "ms_per_step": round(e2e_elapsed / e2e_steps * 1e3, 4),
-                "what": "mul!(y_local, B_r', x) + all_gather of y over RCCL (replicated y on every rank)"},
+                "what": "mul!(y_local, B_r', x) + all_gather of y over RCCL (replicated y on every rank)"}
+        if args.full else None,
         "config": {
             "workload": WORKLOADS[workload] + (f"-scale{args.scale}" if args.scale != 1.0 else ""),
             "op": "mul!(y, B', x) -- transposed 1DVBC (multiply_1DVBC.jl:85-180), stripe-sharded",
@@ -498,6 +539,8 @@ def measure_sharded(args, workload, dtype, world, rank, local, device, forward=F
     }
     if par is not None:
         out["parity"] = par
+    if dumped is not None:
+        out["dump"] = dumped
     if forward:
         out["forward_allreduce"] = {"value": round(bytes_total * e2e_steps / fwd_elapsed / 1e9, 2), "unit": "GB/s",
                                     "ms_per_step": round(fwd_elapsed / e2e_steps * 1e3, 4),
@@ -617,7 +660,7 @@ def run_abi_sharded(args, world):
     devices = list(range(world)) if (nd >= world and not args.same_device) else [0] * world
     cmd = [sys.executable, str(Path(__file__).resolve()), "--abi-sharded-child", ",".join(map(str, devices)),
            "--workload", args.workload, "--dtype", args.dtype, "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--scale", str(args.scale)] + (["--no-parity"] if args.no_parity else [])
+           str(args.warmup), "--scale", str(args.scale), "--full"] + (["--no-parity"] if args.no_parity else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE",
                                                              "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
     try:
@@ -681,8 +724,19 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads")
     ap.add_argument("--no-abi-sharded", action="store_true",
                     help="N > 1: skip the one-process C-ABI sharded leg (secondary.abi_sharded)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, parity against the oracle, device "
+                         "clocks, the secondary workloads; N > 1: the end-to-end and C-ABI sharded legs (each still "
+                         "switched off by its --no-... option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the y of the last timed product of the primary workload to DIR/<name>.npy (N > 1: "
+                         "one slice per rank); an array above the size cap is cut to a fixed seeded sample")
     ap.add_argument("--abi-sharded-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_parity = args.no_secondary = args.no_abi_sharded = True
 
     if args.abi_sharded_child:
         abi_sharded_child(args)
@@ -715,13 +769,16 @@ def main():
 
     if world == 1:
         p = measure(args, args.workload, dtype, device, local, with_cpu=not args.no_cpu_baseline,
-                    with_parity=not args.no_parity)
+                    with_parity=not args.no_parity, dump=args.dump_outputs)
         out = dict(head, value=p["value"], unit=p["unit"], ms_per_step=p["ms_per_step"], scaling="strong",
                    dtype=p["dtype"], config=dict(p["config"], parallelism="single GPU"), gflops=p["gflops"],
                    roofline=p["roofline"], cpu_baseline=p.get("cpu_baseline"), parity=p.get("parity"))
         if "parity" in p:
             out["rel_err"] = p["parity"]["rel_err"]
-        out["device"] = box_info(device)
+        if "dump" in p:
+            out["dump"] = p["dump"]
+        if args.full:
+            out["device"] = box_info(device)
         if not args.no_secondary:
             sec = {}
             for wl, dt in (("fe-fwd", dtype), ("fe3d", dtype), ("fe3d-fwd", dtype), ("ns", dtype), ("c5", np.float32),
@@ -749,12 +806,14 @@ def main():
             dist.init_process_group("nccl", device_id=device)
         else:
             dist.init_process_group("gloo")
-        p = measure_sharded(args, args.workload, dtype, world, rank, local, device)
+        p = measure_sharded(args, args.workload, dtype, world, rank, local, device, dump=args.dump_outputs)
         out = dict(head, value=p["value"], unit=p["unit"], ms_per_step=p["ms_per_step"], scaling="strong",
                    dtype=p["dtype"], config=p["config"], gflops=p["gflops"], roofline=p["roofline"], e2e=p["e2e"],
                    cpu_baseline=None, parity=p.get("parity"))
         if p.get("parity"):
             out["rel_err"] = p["parity"]["rel_err"]
+        if "dump" in p:
+            out["dump"] = p["dump"]
         out["secondary"] = {}
         if not args.no_secondary and args.workload != "ldoor":
             c3 = measure_sharded(args, "ldoor", dtype, world, rank, local, device, forward=True)

@@ -189,7 +189,7 @@ def fresh(args):
                     k, val = kv.split("=", 1)
                     env[k.strip()] = val.strip()
             cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--dtype", args.dtype, "--steps",
-                   str(args.reps), "--no-cpu-baseline", "--no-secondary", "--scale", str(args.scale)]
+                   str(args.reps), "--full", "--no-cpu-baseline", "--no-secondary", "--scale", str(args.scale)]
             if args.nrhs:
                 cmd += ["--nrhs", str(args.nrhs)]
             r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
