@@ -23,8 +23,9 @@
 
 /* ABI version (major*10000 + minor*100 + patch), returned by vbc_version().  A binding checks the major
  * version at load time: 3.x changed vbc_info (VBC_INFO_SIZE bytes, written whole by vbc_get_info) and
- * added the I64 / I32 / BOOL eltypes, the sharded 2D handle and the *_ex sharded product. */
-#define VBC_VERSION 30200
+ * added the I64 / I32 / BOOL eltypes, the sharded 2D handle and the *_ex sharded product; 3.3 added
+ * VBC_CREATE_UPDATABLE and vbc_update_values (vbc_info unchanged). */
+#define VBC_VERSION 30300
 #define VBC_INFO_SIZE 152
 
 #ifdef __cplusplus
@@ -83,6 +84,17 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       P slices whose partial sums meet in LDS (rounding differs ~1 ulp);
                                       vbc_info reports it as planar_split > 1 / planar_mask bit 3. */
 
+#define VBC_CREATE_UPDATABLE 0x20u /* keep a value map on the device so that vbc_update_values can overwrite the
+                                      stored values of every layout of the handle in place (same pattern, new
+                                      values).  May be combined with any other create flag on vbc1d / vbc2d /
+                                      vbc_csc_create[_ex]; the sharded creates refuse it (VBC_INVALID_ARG).  The
+                                      flag changes no layout: arena bytes, layout decisions and products are
+                                      those of the handle created without it.  The map costs 4 bytes per stored
+                                      value slot (padding slots included; counted in vbc_info.device_bytes) and
+                                      stores 32-bit source indices: a val of more than 2^31 - 2 elements is
+                                      refused (VBC_INVALID_ARG).  Create builds the layout on the host three
+                                      times (once for the handle, twice to record the map). */
+
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
                                          X[i*ldx + j], ld >= nrhs); the fused multi-RHS kernel
@@ -95,7 +107,8 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                          multiply_VBC.jl:117-121).  Default (0) is BLAS:
                                          y = alpha*op(B)*x + beta*y.  Both agree at (1, 0). */
 
-typedef struct vbc_handle vbc_handle; /* opaque; immutable after create */
+typedef struct vbc_handle vbc_handle; /* opaque; the layout is immutable after create, the stored values
+                                         only change through vbc_update_values (VBC_CREATE_UPDATABLE) */
 
 /* ---------------------------------------------------------------------------------------------
  * Handles (device-resident matrices)
@@ -122,6 +135,24 @@ VBC_API int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t
                    const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags);
 
 VBC_API int vbc_destroy(vbc_handle *h);
+
+/* New values for an unchanged sparsity pattern: overwrites the stored values of every layout of a handle
+ * created with VBC_CREATE_UPDATABLE (VBC_INVALID_ARG without the flag) by `val`, which has the order and length
+ * contract of create: nval >= ofs[L+1]-1 (1D, 2D) or colptr[n+1]-1 (CSC); a shorter array returns
+ * VBC_DIM_MISMATCH and leaves the handle as it was.  val_dtype: any vbc_dtype, converted to the handle's
+ * compute eltype by the rules of vbc_types.val_dtype (a float val on an integer handle: VBC_UNSUPPORTED_DTYPE);
+ * the conversion happens in the update kernel.  Padding slots stay zero.  No host rebuild, no allocation, and
+ * the arena address never changes.
+ *   mem = VBC_MEM_DEVICE: val is a device pointer on the handle's device; one kernel is enqueued on `stream`
+ *     without synchronising.
+ *   mem = VBC_MEM_HOST: val is staged through the handle's staging buffers; returns when the update is complete.
+ * Ordering: products enqueued on `stream` before the update see the old values, products enqueued on it after
+ * the update see the new ones -- also a B'x that forks onto the handle's side streams, since the forks wait on
+ * an event recorded on the caller's stream and are joined back into it.  The caller must order the update
+ * against products running concurrently on OTHER streams (an event, as for any writer of shared memory).
+ * A HIP graph captured over products of this handle replays with the new values and needs no re-capture.
+ * vbc_info.nnz_hint keeps its create-time value. */
+VBC_API int vbc_update_values(vbc_handle *h, const void *val, int64_t nval, int val_dtype, int mem, void *stream);
 
 /* Type parameters of the *_ex create calls: the reference's SparseMatrix1DVBC{W,Tv,Ti} with any
  * Tv in {Float64, Float32, Int64, Int32, Bool} and Ti in {Int64, Int32}, and the eltype the products

@@ -18,6 +18,7 @@ VBC_F64, VBC_F32, VBC_I64, VBC_I32, VBC_BOOL = range(5)
 VBC_MEM_DEVICE, VBC_MEM_HOST = 0, 1
 VBC_CREATE_TRANSPOSED, VBC_CREATE_FORWARD, VBC_CREATE_MULTI, VBC_CREATE_SERIAL = 0x1, 0x2, 0x4, 0x8
 VBC_CREATE_MULTI_FORWARD = 0x10
+VBC_CREATE_UPDATABLE = 0x20
 VBC_VERSION_MAJOR = 3  # include/vbc.h VBC_VERSION / 10000: the vbc_info layout below is that version's
 VBC_INFO_SIZE = 152
 VBC_MUL_REFERENCE_QUIRKS = 0x1
@@ -28,7 +29,7 @@ VBC_SPLIT_STRIPES, VBC_SPLIT_ROWS, VBC_SPLIT_AUTO = 0, 1, 2
 ABI_SYMBOLS = (
     "vbc1d_create", "vbc2d_create", "vbc_csc_create", "vbc_destroy", "vbc_mul", "vbc_mul_mat",
     "vbc1d_create_ex", "vbc2d_create_ex", "vbc_csc_create_ex", "vbc_mul_ex", "vbc_mul_mat_ex",
-    "vbc_get_info", "vbc_last_error", "vbc_version",
+    "vbc_get_info", "vbc_last_error", "vbc_version", "vbc_update_values",
     "vbc1d_create_sharded", "vbc2d_create_sharded", "vbc_sharded_mul", "vbc_sharded_mul_ex", "vbc_sharded_destroy",
     "vbc_sharded_count", "vbc_sharded_shard", "vbc_sharded_split", "vbc_sharded_xspan",
     "vbcx_partition_equi", "vbcx_partition_strict", "vbcx_partition_overlap",
@@ -107,6 +108,7 @@ def lib():
         L.vbc_csc_create_ex.argtypes = [C.POINTER(P), I64, I64, P, P, P, T, INT, U]
         L.vbc_mul_ex.argtypes = [P, INT, P, INT, I64, I64, P, INT, I64, I64, D, D, INT, P, U]
         L.vbc_destroy.argtypes = [P]
+        L.vbc_update_values.argtypes = [P, P, I64, INT, INT, P]
         L.vbc1d_create_sharded.argtypes = [C.POINTER(P), I64, I64, I64, I64, P, P, P, P, P, I64, T, INT, P, INT, U]
         L.vbc2d_create_sharded.argtypes = [C.POINTER(P), I64, I64, I64, I64, I64, P, I64, P, P, P, P, P, I64, T, INT,
                                            P, INT, U]

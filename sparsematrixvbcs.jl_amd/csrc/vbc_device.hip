@@ -20,6 +20,15 @@ namespace vbc {
 
 static thread_local std::string g_err;
 
+// A recording build of VBC_CREATE_UPDATABLE (create_updatable below): create_common lays the arena out on the
+// host as usual, hands the image over instead of uploading it and returns no handle.  `canon`: the byte
+// ranges of the arena filled from transpose_stripes' values (the value map marks their slots, vbc_handle.h).
+struct MapRecorder {
+    std::vector<char> arena;
+    std::vector<std::pair<size_t, size_t>> canon;
+};
+static thread_local MapRecorder *g_rec = nullptr;
+
 void set_error(const char *fmt, ...)
 {
     char buf[1024];
@@ -2549,7 +2558,13 @@ static int transpose_stripes(const vbc_handle *h, const Stripes &s, const char *
             for (int64_t q = b.q0; q < s.rbeg[l + 1] && gof[s.rows[q]] == b.g; q++) {
                 char *d = dst + (s.rows[q] - a[b.g]) * esz;
                 const char *v = val + (s.voff[l] + (q - s.rbeg[l]) * wl + cc) * esz;
-                if (esz == 8) {
+                if (g_rec) {  // a recording build: tags are copied, never summed, and a slot has one source
+                    static const char zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    if (std::memcmp(d, zero8, (size_t)esz) != 0)
+                        return fail(VBC_INVALID_ARG, "a stripe stores one row twice: such a matrix cannot be "
+                                                     "VBC_CREATE_UPDATABLE in a layout of its transpose");
+                    std::memcpy(d, v, (size_t)esz);
+                } else if (esz == 8) {
                     double t, u2;
                     std::memcpy(&t, d, 8);
                     std::memcpy(&u2, v, 8);
@@ -2759,6 +2774,7 @@ static void release(vbc_handle *h)
         if (l.d_pbins) (void)hipFree(l.d_pbins);
     }
     if (h->d_arena) (void)hipFree(h->d_arena);
+    if (h->umap.d_buf) (void)hipFree(h->umap.d_buf);
     if (h->d_carry_mm) (void)hipFree(h->d_carry_mm);
     for (void *p : h->d_stage)
         if (p) (void)hipFree(p);
@@ -2795,7 +2811,11 @@ static int create_int(vbc_handle *h, const Stripes &s, const int64_t *val, int64
     std::memcpy(ar.at<int64_t>(o_rbeg), s.rbeg.data(), (L + 1) * 8);
     if (q) std::memcpy(ar.at<int32_t>(o_rows), s.rows.data(), q * 4);
     if (nval) std::memcpy(ar.at<int64_t>(o_val), val, nval * 8);
-    h->arena_bytes = ar.host.size();
+    h->arena_bytes = h->arena_used = ar.host.size();
+    if (g_rec) {
+        g_rec->arena = std::move(ar.host);
+        return VBC_OK;
+    }
     VBC_HIP(hipMalloc(&h->d_arena, h->arena_bytes));
     VBC_HIP(hipMemcpy(h->d_arena, ar.host.data(), h->arena_bytes, hipMemcpyHostToDevice));
     char *b = static_cast<char *>(h->d_arena);
@@ -2851,6 +2871,7 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
     }
     if (dtype == VBC_I64) {  // exact integer products (vbc_generic.hip): one layout, both directions
         if (int st = create_int(h, s, static_cast<const int64_t *>(val), nval)) { release(h); return st; }
+        if (g_rec) { release(h); return VBC_OK; }
         h->has_t = (flags & (VBC_CREATE_TRANSPOSED | VBC_CREATE_MULTI)) != 0;
         h->has_f = (flags & (VBC_CREATE_FORWARD | VBC_CREATE_MULTI_FORWARD)) != 0;
         *out = h;
@@ -2983,7 +3004,9 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
     }
     std::vector<PendingPanel> pmf;
     if (st == VBC_OK && (flags & VBC_CREATE_MULTI_FORWARD)) {
+        const size_t c0 = ar.host.size();
         st = build_forward_panel(h, s, v, ar, pmf, h->lmf);
+        if (g_rec) g_rec->canon.emplace_back(c0, ar.host.size());
         h->has_mf = st == VBC_OK;
         if (st == VBC_OK) h->lmf.o_fill = ar.reserve(4);
     }
@@ -3008,7 +3031,9 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
         st = transpose_stripes(h, s, v, 8, c, cv);
         if (st == VBC_OK) {
             const int64_t bt = h->bytes_t;
+            const size_t c0 = ar.host.size();
             st = build_transposed(h, c, cv.data(), ar, ptf, stf, swf, h->lft, fill_tf);
+            if (g_rec) g_rec->canon.emplace_back(c0, ar.host.size());
             h->bytes_f = h->bytes_t - bt;
             h->bytes_t = bt;
         }
@@ -3029,6 +3054,12 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
         }
     }
     if (st != VBC_OK) { release(h); return st; }
+    h->arena_used = ar.host.size();
+    if (g_rec) {
+        g_rec->arena = std::move(ar.host);
+        release(h);
+        return VBC_OK;
+    }
     h->arena_bytes = std::max<size_t>(ar.host.size(), 256);
     if (hipMalloc(&h->d_arena, h->arena_bytes) != hipSuccess) {
         release(h);
@@ -3097,9 +3128,52 @@ int vbc_last_error(char *buf, size_t n)
     return (int)g_err.size();
 }
 
-int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
-                 const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                 int64_t nval, int dtype, int device, unsigned flags)
+extern "C++" {
+// VBC_CREATE_UPDATABLE: the plain create (which validates everything and is the handle the caller gets), then
+// two recording builds of the same pattern -- val all zero, val holding the tag i + 1 in element i, written
+// before any blocking or transposition of the values -- whose arenas differ exactly in the value slots
+// (vbc_update.hip build_value_map).  create(out, val, nval): the entry point's own body; val = NULL: the caller's.
+template <typename F>
+static int create_updatable(vbc_handle **out, F &&create)
+{
+    if (!out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
+    *out = nullptr;
+    vbc_handle *h = nullptr;
+    if (int st = create(&h, nullptr, 0)) return st;
+    const int64_t nv = h->nval;
+    const size_t esz = (size_t)h->esz;
+    int st = VBC_OK;
+    if (nv > kUpdMaxSource) st = fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
+    MapRecorder rec[2];
+    std::vector<char> tv((size_t)std::max<int64_t>(nv, 1) * esz, 0);
+    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
+        if (pass == 1)
+            for (int64_t i = 0; i < nv; i++) {
+                const uint64_t tag = (uint64_t)i + 1;
+                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
+            }
+        vbc_handle *none = nullptr;
+        g_rec = &rec[pass];
+        st = create(&none, tv.data(), nv);
+        g_rec = nullptr;
+    }
+    tv = std::vector<char>();
+    if (st == VBC_OK && rec[0].arena.size() != h->arena_used)
+        st = fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
+    if (st == VBC_OK) {
+        DeviceGuard g(h->device);
+        st = g.ok ? build_value_map(h, rec[1].arena, rec[0].arena, rec[1].canon) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
+    }
+    if (st != VBC_OK) { release(h); return st; }
+    h->updatable = true;
+    *out = h;
+    return VBC_OK;
+}
+}  // extern "C++"
+
+static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
+                     const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
+                     int64_t nval, int dtype, int device, unsigned flags)
 {
     // SparseMatrix1DVBC{W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:45-50)
     if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
@@ -3136,10 +3210,22 @@ int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, c
     return create_common(out, s, val, dtype, device, flags, ofs[L] - 1, 0, q);
 }
 
-int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
-                 const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
-                 const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
-                 int device, unsigned flags)
+int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
+                 const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
+                 int64_t nval, int dtype, int device, unsigned flags)
+{
+    if (!(flags & VBC_CREATE_UPDATABLE))
+        return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
+    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
+    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t nv) {
+        return create_1d(o, m, n, W, L, spl, pos, idx, ofs, v ? v : val, v ? nv : nval, dtype, device, f);
+    });
+}
+
+static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
+                     const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
+                     const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
+                     int device, unsigned flags)
 {
     // SparseMatrixVBC{U,W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:72-79)
     if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
@@ -3199,8 +3285,21 @@ int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, i
     return create_common(out, s, val, dtype, device, flags, ofs[L] - 1, K, q);
 }
 
-int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
-                   const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
+int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
+                 const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
+                 const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
+                 int device, unsigned flags)
+{
+    if (!(flags & VBC_CREATE_UPDATABLE))
+        return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
+    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
+    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t nv) {
+        return create_2d(o, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, v ? v : val, v ? nv : nval, dtype, device, f);
+    });
+}
+
+static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
+                      const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
 {
     if (m < 0 || n < 0) return fail(VBC_INVALID_ARG, "number of rows/columns must be >= 0");
     if (!colptr || colptr[0] != 1) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
@@ -3273,6 +3372,17 @@ int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr
     return create_common(out, s, nzval, dtype, device, flags, nnz, 0, nnz);
 }
 
+int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
+                   const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
+{
+    if (!(flags & VBC_CREATE_UPDATABLE)) return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags);
+    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
+    // the tags go into an nzval-shaped array, before the column blocking below copies them into its stripes
+    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t) {
+        return create_csc(o, m, n, colptr, rowval, v ? v : nzval, dtype, device, f);
+    });
+}
+
 int vbc_destroy(vbc_handle *h)
 {
     release(h);
@@ -3299,7 +3409,7 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     if (h->has_ft) bf += (int32_t)(h->lft.bins.size() + h->lft.sbins.size() + h->lft.pbins.size() + h->lft.wbins.size());
     info->bins_f = h->has_f ? bf : 0;
     if (h->has_ft) info->planar_mask |= 256;  // the forward product runs on the transposed layout of C = Bᵀ
-    info->device_bytes = (int64_t)h->arena_bytes;
+    info->device_bytes = (int64_t)(h->arena_bytes + h->umap.bytes);  // the value map of an updatable handle included
     info->bytes_t = h->bytes_t;
     info->bytes_f = h->bytes_f;
     info->bins_m = h->has_m ? (int32_t)(h->lm.bins.size() + h->lm.tbins.size())
@@ -3729,6 +3839,42 @@ int vbc_mul_mat_ex(vbc_handle *h, int trans, int64_t nrhs, const void *X, int X_
         return fail(VBC_UNSUPPORTED_DTYPE, "the matrix product takes X and Y of the handle's compute eltype "
                                            "(other eltypes: vbc_mul_ex column by column)");
     return vbc_mul_mat(h, trans, nrhs, X, ldx, nx, Y, ldy, ny, alpha, beta, mem, stream, flags);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Value updates of a handle with an unchanged pattern (VBC_CREATE_UPDATABLE)
+// ---------------------------------------------------------------------------------------------
+
+int vbc_update_values(vbc_handle *h, const void *val, int64_t nval, int val_dtype, int mem, void *stream)
+{
+    if (!h) return fail(VBC_INVALID_ARG, "NULL handle");
+    if (!h->updatable) return fail(VBC_INVALID_ARG, "handle created without VBC_CREATE_UPDATABLE");
+    if (!known_dtype(val_dtype)) return fail(VBC_UNSUPPORTED_DTYPE, "unknown val_dtype");
+    if (h->dtype == VBC_I64 && is_float(val_dtype))
+        return fail(VBC_UNSUPPORTED_DTYPE, "floating-point values on an integer handle (InexactError)");
+    if (nval < h->nval) return fail(VBC_DIM_MISMATCH, "DimensionMismatch: val shorter than at create");
+    if (h->nval > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
+    if (mem != VBC_MEM_DEVICE && mem != VBC_MEM_HOST)
+        return fail(VBC_INVALID_ARG, "mem must be VBC_MEM_DEVICE or VBC_MEM_HOST");
+    if (h->nval == 0) return VBC_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    if (mem == VBC_MEM_DEVICE) return update_launch(h, val, val_dtype, s);  // one kernel, ordered by the stream
+    // host val: through the x staging buffer, in the handle's product order (a product on another stream
+    // may be reading that buffer)
+    std::lock_guard<std::mutex> lk(h->mu);
+    const size_t bytes = (size_t)h->nval * elem_size(val_dtype);
+    void *dv = nullptr;
+    if (int st = stage_buffer(h, 0, bytes, &dv)) return st;
+    ProductOrder po(h, s, true);
+    if (int st = po.begin()) return st;
+    if (hipMemcpyAsync(dv, val, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(VBC_HIP_ERROR, "staging copy of val failed");
+    if (int st = update_launch(h, dv, val_dtype, s)) return st;
+    if (int st = po.end()) return st;
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(VBC_HIP_ERROR, "hipStreamSynchronize failed");
+    return VBC_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "vbc_internal.h"
@@ -92,6 +93,29 @@ struct Stripes {
     std::vector<int64_t> grp;   // 2D input: Π's block-row starts (K + 1, 0-based); empty for 1D / CSC
 };
 
+// VBC_CREATE_UPDATABLE (vbc_update.hip): the value map of a handle.  `map` holds one 32-bit entry per stored
+// value slot, in arena order: the index of the source element of the caller's val, kUpdCanon set where the
+// create path stores 0 + v (transpose_stripes), kUpdZero for a padding slot (rewritten with zero) or kUpdSkip
+// for a word that is no value slot (alignment of a region to 16 bytes; never written).  The entries are cut
+// into chunks of at most kUpdChunkQuads 16-byte quads: `dst` and `map` are element offsets (multiples of a
+// quad) into the arena and the map, 64 bits wide, so only the source index is limited to 32 bits.
+struct UpdChunk {
+    uint64_t dst;
+    uint64_t map;
+    uint32_t n;  // quads
+    uint32_t pad;
+};
+constexpr uint32_t kUpdZero = 0xFFFFFFFFu, kUpdSkip = 0xFFFFFFFEu, kUpdCanon = 0x80000000u;
+constexpr int64_t kUpdMaxSource = 0x7FFFFFFE;  // largest nval an updatable handle takes (entries keep bit 31 free)
+constexpr int kUpdChunkQuads = 1024;
+struct ValueMap {
+    void *d_buf = nullptr;  // map entries, then the chunk table
+    size_t bytes = 0;
+    const uint32_t *d_map = nullptr;
+    const UpdChunk *d_chunks = nullptr;
+    int64_t nchunks = 0, entries = 0;
+};
+
 }  // namespace vbc
 
 struct vbc_handle {
@@ -99,6 +123,9 @@ struct vbc_handle {
     int dtype = 0, esz = 8, device = 0;
     void *d_arena = nullptr;
     size_t arena_bytes = 0;
+    size_t arena_used = 0;        // bytes of the host image the arena was uploaded from
+    bool updatable = false;       // VBC_CREATE_UPDATABLE: `umap` is built, vbc_update_values is allowed
+    vbc::ValueMap umap;
     bool has_t = false, has_f = false, has_m = false;
     vbc::PanelLaunch lm;          // multi-RHS transposed product on matrix cores (VBC_CREATE_MULTI)
     int64_t bytes_m = 0;          // matrix bytes one panel product streams
@@ -235,6 +262,10 @@ void occupancy_ranges(int esz, int K, int P, int occ[2]);
 int mul_int(const vbc_handle *h, int trans, const void *x, void *y, double alpha, double beta, hipStream_t s);
 int convert_gather(const void *src, int src_dtype, int64_t inc, void *dst, int dst_dtype, int64_t n, hipStream_t s);
 int convert_scatter(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t inc, int64_t n, hipStream_t s);
+// vbc_update.hip
+int build_value_map(vbc_handle *h, const std::vector<char> &tagged, const std::vector<char> &zeroed,
+                    const std::vector<std::pair<size_t, size_t>> &canon);
+int update_launch(const vbc_handle *h, const void *d_val, int val_dtype, hipStream_t s);
 // vbc_panel_launch.hip
 int mulmat_panel_any(const vbc_handle *h, int trans, int64_t nrhs, const char *X, int64_t sxr, int64_t sxc, char *Y,
                      int64_t syr, int64_t syc, double alpha, double beta, hipStream_t s);

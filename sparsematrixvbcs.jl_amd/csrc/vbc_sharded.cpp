@@ -557,6 +557,8 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
     *out = nullptr;
     if (!types) return vbc::fail(VBC_INVALID_ARG, "NULL vbc_types");
     if (ngpus < 1 || !devices) return vbc::fail(VBC_INVALID_ARG, "ngpus must be >= 1 with a device list");
+    if (flags & VBC_CREATE_UPDATABLE)  // the shards are built from re-sliced values: their maps would need composing
+        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE is not supported on sharded handles");
     if (split != VBC_SPLIT_STRIPES && split != VBC_SPLIT_ROWS && split != VBC_SPLIT_AUTO)
         return vbc::fail(VBC_INVALID_ARG, "split must be VBC_SPLIT_STRIPES, VBC_SPLIT_ROWS or VBC_SPLIT_AUTO");
     int count = 0;

@@ -83,7 +83,8 @@ end
     HIPSparseMatrix1DVBC(B::SparseMatrix1DVBC; device=0, forward=true, transposed=true)
 
 Device-resident copies of `B`, one libvbc handle per compute eltype met (created on first use by
-`mul!`), freed by a finalizer (`vbc_destroy`).  Immutable.
+`mul!`), freed by a finalizer (`vbc_destroy`).  The layout is immutable; with `updatable=true`
+(VBC_CREATE_UPDATABLE) `update_values!(M, val)` overwrites the stored values in place.
 """
 mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
     host::SparseMatrix1DVBC{W, Tv, Ti}
@@ -93,9 +94,10 @@ mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
 end
 
 function HIPSparseMatrix1DVBC(B::SparseMatrix1DVBC{W, Tv, Ti}; device::Integer=0, forward::Bool=true,
-                              transposed::Bool=true, multi::Bool=false) where {W, Tv, Ti}
+                              transposed::Bool=true, multi::Bool=false, updatable::Bool=false) where {W, Tv, Ti}
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
-            (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0))
+            (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0))
     M = HIPSparseMatrix1DVBC{W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -119,9 +121,10 @@ mutable struct HIPSparseMatrixVBC{U, W, Tv, Ti}
 end
 
 function HIPSparseMatrixVBC(B::SparseMatrixVBC{U, W, Tv, Ti}; device::Integer=0, forward::Bool=true,
-                            transposed::Bool=true, multi::Bool=false) where {U, W, Tv, Ti}
+                            transposed::Bool=true, multi::Bool=false, updatable::Bool=false) where {U, W, Tv, Ti}
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
-            (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0))
+            (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0))
     M = HIPSparseMatrixVBC{U, W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -146,8 +149,9 @@ mutable struct HIPSparseMatrixCSC{Tv, Ti}
     handles::Dict{Cint, Ptr{Cvoid}}
 end
 
-function HIPSparseMatrixCSC(A::SparseMatrixCSC{Tv, Ti}; device::Integer=0) where {Tv, Ti}
-    M = HIPSparseMatrixCSC{Tv, Ti}(A, device, VBC_CREATE_TRANSPOSED, Dict{Cint, Ptr{Cvoid}}())
+function HIPSparseMatrixCSC(A::SparseMatrixCSC{Tv, Ti}; device::Integer=0, updatable::Bool=false) where {Tv, Ti}
+    M = HIPSparseMatrixCSC{Tv, Ti}(A, device, VBC_CREATE_TRANSPOSED | (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)),
+                                   Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
 end
@@ -171,6 +175,31 @@ function handle_for(A::HIPMatrix, ::Type{Ty}) where {Ty}
     cdt = compute_dtype(Ty)
     cdt == VBC_I64 && eltype(A) <: AbstractFloat && throw(InexactError(:convert, Ty, zero(eltype(A))))
     get!(() -> _create(A.host, A.device, A.flags, cdt), A.handles, cdt)
+end
+
+_host_values(A::HIPSparseMatrixCSC) = A.host.nzval
+_host_values(A::HIPMatrix) = A.host.val
+
+"""
+    update_values!(A, val::StridedVector)
+
+New values for the same sparsity pattern (vbc_update_values): `val`, ordered like the host struct's `val`
+(`nzval` for a CSC operand) and at least as long as the stored values, replaces them on the host and in
+every handle of `A`, in place -- no re-create, captured graphs stay valid.  `A` must have been made with
+`updatable=true` (ArgumentError otherwise).  Host vectors return when the update is complete.
+"""
+function update_values!(A::HIPMatrix, val::StridedVector{Tn}) where {Tn}
+    A.flags & VBC_CREATE_UPDATABLE == 0 && throw(ArgumentError("update_values! needs updatable=true"))
+    stride(val, 1) == 1 || throw(ArgumentError("val must be contiguous"))
+    for h in values(A.handles)
+        GC.@preserve val check(ccall((:vbc_update_values, libvbc), Cint,
+            (Ptr{Cvoid}, Ptr{Tn}, Int64, Cint, Cint, Ptr{Cvoid}),
+            h, pointer(val), length(val), vbc_dtype(Tn), VBC_MEM_HOST, C_NULL))
+    end
+    hv = _host_values(A)
+    k = min(length(hv), length(val))
+    copyto!(hv, 1, val, 1, k)
+    return A
 end
 
 function destroy_handles(A::HIPMatrix)
@@ -233,6 +262,7 @@ end
 const HIPShardedSparseMatrix1DVBC = HIPShardedSparseMatrix  # round-2 name
 
 const VBC_CREATE_SERIAL = Cuint(8)
+const VBC_CREATE_UPDATABLE = Cuint(0x20)
 
 _split_code(split) = split === :stripes ? VBC_SPLIT_STRIPES : split === :rows ? VBC_SPLIT_ROWS : VBC_SPLIT_AUTO
 
@@ -351,7 +381,7 @@ LinearAlgebra.mul!(Y::StridedMatrix, adjA::AdjOrTransHIP, X::StridedMatrix, α::
     _mul_cols!(Y, adjA, X, α, β)
 LinearAlgebra.mul!(Y::StridedMatrix, A::HIPMatrix, X::StridedMatrix, α::Number, β::Number) = _mul_cols!(Y, A, X, α, β)
 
-export HIPShardedSparseMatrix
+export HIPShardedSparseMatrix, update_values!
 export HIPSparseMatrix1DVBC, HIPSparseMatrixVBC, HIPSparseMatrixCSC, HIPShardedSparseMatrix1DVBC, TrSpMV!
 
 end # module

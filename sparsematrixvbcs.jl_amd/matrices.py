@@ -80,18 +80,20 @@ class _DeviceMatrix:
             flags = _L.VBC_CREATE_MULTI if trans else _L.VBC_CREATE_MULTI_FORWARD
         else:
             flags = _L.VBC_CREATE_TRANSPOSED if trans else _L.VBC_CREATE_FORWARD
-        compute = _L.compute_code(self.val.dtype) if compute is None else int(compute)
-        if compute == _L.VBC_I64 and self.val.dtype.kind == "f":
+        compute = _L.compute_code(self._val.dtype) if compute is None else int(compute)
+        if compute == _L.VBC_I64 and self._val.dtype.kind == "f":
             raise _L.UnsupportedDtype("a floating-point matrix cannot run in an integer eltype (InexactError)")
         if multi and compute == _L.VBC_I64:  # integer eltypes: one SpMV per column
             flags = _L.VBC_CREATE_TRANSPOSED if trans else _L.VBC_CREATE_FORWARD
         if getattr(self, "serial", False) and not multi:
             flags |= _L.VBC_CREATE_SERIAL  # the reference's serial per-stripe order in every layout
+        if getattr(self, "updatable", False):
+            flags |= _L.VBC_CREATE_UPDATABLE  # update_values rewrites the stored values in place
         return self._handles.get((int(device), flags, compute),
                                  lambda out: self._create(out, int(device), flags, compute))
 
     def _types(self, compute):
-        return _L.vbc_types(_L.dtype_code(self.val.dtype), 64, compute, 0)
+        return _L.vbc_types(_L.dtype_code(self._val.dtype), 64, compute, 0)
 
     def info(self, device=0, trans=True, multi=False, compute=None):
         inf = _L.vbc_info()
@@ -100,6 +102,78 @@ class _DeviceMatrix:
 
     def release(self):
         self._handles.release()
+
+    # `val` is the host copy of the values.  After update_values(tensor) it is taken from that tensor only when
+    # somebody reads it, so an update from device memory never waits for the GPU.
+    @property
+    def val(self):
+        pending = self.__dict__.get("_val_dev")
+        if pending is not None:
+            self._val_dev = None
+            self._val = self._host_values(pending.detach().cpu().numpy())
+        return self._val
+
+    @val.setter
+    def val(self, v):
+        self._val_dev = None
+        self._val = v
+
+    def _nval_needed(self):
+        return int(self.ofs[-1]) - 1
+
+    def _host_values(self, v):
+        """v as the matrix's own host array: its eltype and length (the SIMD tail pad stays zero)."""
+        old = self._val
+        new = np.zeros_like(old)
+        k = min(len(old), len(v))
+        new[:k] = v[:k].astype(old.dtype, copy=False)
+        return new
+
+    def update_values(self, val, stream=None):
+        """New values for the same sparsity pattern (vbc.h vbc_update_values): `val` -- a numpy array or a torch
+        tensor on a handle's device, ordered like `B.val` and at least ofs[L+1]-1 long (nzval: colptr[n+1]-1) --
+        replaces the host copy `B.val` and is written into every live handle of the matrix in place: no
+        host rebuild, no reallocation, captured HIP graphs stay valid.  Needs `B.updatable = True`, set
+        before the first product.  A tensor is enqueued on `stream` (default: torch's current stream of its
+        device) without synchronising; products enqueued there afterwards see the new values.  The tensor
+        is kept (not copied) until `B.val` is next read, so overwrite it only together with another update."""
+        if not getattr(self, "updatable", False):
+            raise _L.ArgumentError("update_values needs an updatable matrix: set B.updatable = True before the "
+                                   "first product (handles are not re-created silently)")
+        if len(val.shape) != 1:
+            raise _L.ArgumentError("val must be a vector")
+        if val.shape[0] < self._nval_needed():
+            raise _L.DimensionMismatch(f"val has {val.shape[0]} elements, the pattern stores {self._nval_needed()}")
+        code = _L.dtype_code(val.dtype)
+        if self._val.dtype.kind != "f" and code in (_L.VBC_F64, _L.VBC_F32):
+            raise _L.UnsupportedDtype("floating-point values for an integer matrix (InexactError)")
+        is_torch = type(val).__module__.startswith("torch")
+        host = None
+        if is_torch:
+            if not val.is_cuda:
+                raise _L.ArgumentError("a torch val must live on a GPU (pass a numpy array for host values)")
+            if not val.is_contiguous():
+                raise _L.ArgumentError("val must be contiguous")
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(val.device).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+        else:
+            host = np.ascontiguousarray(val)
+        for (dev, _flags, _compute), hp in self._handles.h.items():
+            if is_torch and dev == val.device.index:
+                st = _L.lib().vbc_update_values(hp, val.data_ptr(), val.shape[0], code, _L.VBC_MEM_DEVICE, stream)
+            else:
+                if host is None:  # a handle on another device than the tensor's
+                    host = val.detach().cpu().numpy()
+                st = _L.lib().vbc_update_values(hp, host.ctypes.data, len(host), code, _L.VBC_MEM_HOST, None)
+            _L.check(st, "update_values")
+        if host is not None:
+            self.val = self._host_values(host)
+        else:
+            self._val_dev = val  # (an earlier pending tensor is superseded)
+        return self
 
     @property
     def shape(self):
@@ -110,7 +184,7 @@ class _DeviceMatrix:
 
     @property
     def dtype(self):
-        return self.val.dtype
+        return self._val.dtype
 
     # adjoint / transpose views (LinearAlgebra.Adjoint / Transpose)
     @property
@@ -166,6 +240,12 @@ class SparseMatrix1DVBC(_DeviceMatrix):
         (m, n), colptr, rowval, nzval = _csc_fields(A)
         if dtype is not None:
             nzval = nzval.astype(dtype)
+        pos, idx, ofs, val = cls._fill(W, m, n, colptr, rowval, nzval, Phi)
+        return cls(W, m, n, Phi, pos, idx, ofs, val)
+
+    @staticmethod
+    def _fill(W, m, n, colptr, rowval, nzval, Phi):
+        """pos, idx, ofs, val of A under Φ (the reference's constructor, constructors_1DVBC.jl:9-60)."""
         lib = _L.lib()
         L = len(Phi)
         pos = np.zeros(L + 1, np.int64)
@@ -179,7 +259,19 @@ class SparseMatrix1DVBC(_DeviceMatrix):
                                      _L.dtype_code(nzval.dtype), L, Phi.spl.ctypes.data, pos.ctypes.data,
                                      ofs.ctypes.data, idx.ctypes.data, val.ctypes.data, pad),
                  "SparseMatrix1DVBC")
-        return cls(W, m, n, Phi, pos, idx, ofs, val)
+        return pos, idx, ofs, val
+
+    def update_from_csc(self, A):
+        """A with the same sparsity pattern and new nzval: the host fill with the matrix's own Φ, a check that
+        pos, idx and ofs come out identical (ArgumentError otherwise), then update_values."""
+        (m, n), colptr, rowval, nzval = _csc_fields(A)
+        if (m, n) != (self.m, self.n):
+            raise _L.ArgumentError("sparsity pattern changed")
+        pos, idx, ofs, val = self._fill(self.W, m, n, colptr, rowval, nzval.astype(self._val.dtype, copy=False),
+                                        self.Phi)
+        if not (np.array_equal(pos, self.pos) and np.array_equal(ofs, self.ofs) and np.array_equal(idx, self.idx)):
+            raise _L.ArgumentError("sparsity pattern changed")
+        return self.update_values(val)
 
     def _create(self, out, device, flags, compute):
         spl = self.Phi.spl
@@ -189,7 +281,7 @@ class SparseMatrix1DVBC(_DeviceMatrix):
                                         self.val.ctypes.data, len(self.val), C.byref(t), device, flags)
 
     def __repr__(self):
-        return (f"SparseMatrix1DVBC{{{self.W},{self.val.dtype},Int64}}({self.m}×{self.n}, "
+        return (f"SparseMatrix1DVBC{{{self.W},{self._val.dtype},Int64}}({self.m}×{self.n}, "
                 f"{len(self.Phi)} stripes, {len(self.idx)} row-blocks)")
 
 
@@ -248,6 +340,12 @@ class SparseMatrixVBC(_DeviceMatrix):
         (m, n), colptr, rowval, nzval = _csc_fields(A)
         if dtype is not None:
             nzval = nzval.astype(dtype)
+        pos, idx, ofs, val = cls._fill(U, W, m, n, colptr, rowval, nzval, Pi, Phi)
+        return cls(U, W, m, n, Pi, Phi, pos, idx, ofs, val)
+
+    @staticmethod
+    def _fill(U, W, m, n, colptr, rowval, nzval, Pi, Phi):
+        """pos, idx, ofs, val of A under (Π, Φ) (the reference's constructor, constructors_VBC.jl:15-130)."""
         lib = _L.lib()
         K, L = len(Pi), len(Phi)
         pos = np.zeros(L + 1, np.int64)
@@ -261,7 +359,19 @@ class SparseMatrixVBC(_DeviceMatrix):
                                    _L.dtype_code(nzval.dtype), K, Pi.spl.ctypes.data, L, Phi.spl.ctypes.data,
                                    pos.ctypes.data, ofs.ctypes.data, idx.ctypes.data, val.ctypes.data, pad),
                  "SparseMatrixVBC")
-        return cls(U, W, m, n, Pi, Phi, pos, idx, ofs, val)
+        return pos, idx, ofs, val
+
+    def update_from_csc(self, A):
+        """A with the same sparsity pattern and new nzval: the host fill with the matrix's own Π and Φ, a check
+        that pos, idx and ofs come out identical (ArgumentError otherwise), then update_values."""
+        (m, n), colptr, rowval, nzval = _csc_fields(A)
+        if (m, n) != (self.m, self.n):
+            raise _L.ArgumentError("sparsity pattern changed")
+        pos, idx, ofs, val = self._fill(self.U, self.W, m, n, colptr, rowval,
+                                        nzval.astype(self._val.dtype, copy=False), self.Pi, self.Phi)
+        if not (np.array_equal(pos, self.pos) and np.array_equal(ofs, self.ofs) and np.array_equal(idx, self.idx)):
+            raise _L.ArgumentError("sparsity pattern changed")
+        return self.update_values(val)
 
     def _create(self, out, device, flags, compute):
         t = self._types(compute)
@@ -271,7 +381,7 @@ class SparseMatrixVBC(_DeviceMatrix):
                                         len(self.val), C.byref(t), device, flags)
 
     def __repr__(self):
-        return (f"SparseMatrixVBC{{{self.U},{self.W},{self.val.dtype},Int64}}({self.m}×{self.n}, "
+        return (f"SparseMatrixVBC{{{self.U},{self.W},{self._val.dtype},Int64}}({self.m}×{self.n}, "
                 f"{len(self.Pi)}×{len(self.Phi)} partition, {len(self.idx)} blocks)")
 
 
@@ -279,9 +389,15 @@ class SparseMatrixCSC(_DeviceMatrix):
     """SparseMatrixCSC{Tv,Int64} fields (colptr, rowval, nzval), the operand of TrSpMV!."""
 
     def __init__(self, A):
-        (self.m, self.n), self.colptr, self.rowval, self.nzval = _csc_fields(A)
-        self.val = self.nzval
+        (self.m, self.n), self.colptr, self.rowval, self.val = _csc_fields(A)
         self._init_handles()
+
+    @property
+    def nzval(self):  # the reference's field name; update_values(nzval) replaces it
+        return self.val
+
+    def _nval_needed(self):
+        return int(self.colptr[-1]) - 1
 
     def _create(self, out, device, flags, compute):
         t = self._types(compute)

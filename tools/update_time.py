@@ -1,0 +1,141 @@
+"""What a value update costs (vbc.h vbc_update_values) against the only other route, destroy + create.
+
+For one workload per process (a fresh process per matrix, as bench.py measures), B'x handle:
+  (a) vbc_update_values from a device val: events around a HIP graph of K updates, after warm-up;
+  (b) the same from a host val (staging copy + kernel + synchronise; wall clock);
+  (c) destroy + create with the new values, not updatable (wall clock);
+  (d) create with and without VBC_CREATE_UPDATABLE (wall clock);
+  (e) one product (events around a graph of K products).
+The update moves about slots x (2 esz + 4) bytes (source value, stored value, map entry); slots is taken from
+the map's size, (device_bytes with the flag - device_bytes without) / 4.  (a) is also given as the fraction of
+8 TB/s that traffic reaches.  One JSON line; --out writes it to a file as well.
+
+    python tools/update_time.py --workload fe|ldoor [--scale 1.0] [--steps 20] [--warmup 5] [--out FILE]
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def graph_time_us(torch, s, fn, steps, warmup, reps=5):
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(steps):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(s):
+            e0.record(s)
+            g.replay()
+            e1.record(s)
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e3 / steps)
+    return float(np.median(times)), [round(t, 2) for t in times]
+
+
+def wall_ms(torch, fn, reps):
+    times = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times)), [round(t, 1) for t in times]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="fe", choices=["fe", "ldoor"])
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    import bench
+    import sparsematrixvbcs_amd as V
+
+    B = bench.build_matrix(args.workload, np.float64, args.scale)
+    esz = B.val.dtype.itemsize
+    rng = np.random.default_rng(7)
+    v2 = rng.uniform(-1, 1, len(B.val))
+    d2 = torch.from_numpy(v2).cuda()
+
+    def plain():
+        return V.SparseMatrix1DVBC(B.W, B.m, B.n, B.Phi, B.pos, B.idx, B.ofs, B.val)
+
+    # (d) create, with and without the flag (one each: the host build dominates and is deterministic work)
+    P = plain()
+    create_plain, _ = wall_ms(torch, lambda: P.handle(0, True), 1)
+    U = plain()
+    U.updatable = True
+    create_upd, _ = wall_ms(torch, lambda: U.handle(0, True), 1)
+    inf_p, inf_u = P.info(), U.info()
+    slots = (inf_u["device_bytes"] - inf_p["device_bytes"]) // 4
+    traffic = slots * (2 * esz + 4)
+
+    # (c) destroy + create with new values: what a caller without the flag has to do
+    def recreate():
+        P.release()
+        P.val = v2
+        P.handle(0, True)
+    recreate_ms, recreate_all = wall_ms(torch, recreate, 2)
+
+    s = torch.cuda.Stream()
+    x = torch.from_numpy(rng.uniform(-1, 1, B.m)).cuda()
+    y = torch.empty(B.n, dtype=torch.float64, device="cuda")
+    h = U.handle(0, True)
+    lib, L = V._lib.lib(), V._lib
+
+    def update_dev():
+        L.check(lib.vbc_update_values(h, d2.data_ptr(), len(v2), L.VBC_F64, L.VBC_MEM_DEVICE, s.cuda_stream))
+    upd_us, upd_all = graph_time_us(torch, s, update_dev, args.steps, args.warmup)
+    # (b) host val
+    host_ms, host_all = wall_ms(torch, lambda: L.check(lib.vbc_update_values(h, v2.ctypes.data, len(v2), L.VBC_F64,
+                                                                              L.VBC_MEM_HOST, None)), 3)
+    prod_us, prod_all = graph_time_us(torch, s, lambda: V.mul_(y, U.T, x), args.steps, args.warmup)
+    # the updated handle computes what the re-created one computes
+    y2 = torch.empty_like(y)
+    V.mul_(y2, P.T, x)
+    V.mul_(y, U.T, x)
+    torch.cuda.synchronize()
+    out = {
+        "tool": "update_time", "workload": args.workload, "scale": args.scale, "dtype": "float64",
+        "m": B.m, "n": B.n, "nval": int(B.ofs[-1]) - 1, "value_slots": int(slots), "map_bytes": int(slots * 4),
+        "arena_bytes": inf_p["device_bytes"],
+        "update_device_us": round(upd_us, 2), "update_device_us_all": upd_all,
+        "update_traffic_bytes": int(traffic), "update_frac_of_8TBs": round(traffic / (upd_us * 1e-6) / 8e12, 3),
+        "update_host_ms": round(host_ms, 2), "update_host_ms_all": host_all,
+        "recreate_ms": round(recreate_ms, 1), "recreate_ms_all": recreate_all,
+        "create_ms": round(create_plain, 1), "create_updatable_ms": round(create_upd, 1),
+        "product_us": round(prod_us, 2), "product_us_all": prod_all,
+        "update_below_recreate": bool(upd_us * 1e-3 < recreate_ms),
+        "bitwise_equal_to_recreated": bool(torch.equal(y, y2)),
+        "steps": args.steps, "warmup": args.warmup,
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    return 0 if out["update_below_recreate"] and out["bitwise_equal_to_recreated"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
