@@ -24,8 +24,9 @@
 /* ABI version (major*10000 + minor*100 + patch), returned by vbc_version().  A binding checks the major
  * version at load time: 3.x changed vbc_info (VBC_INFO_SIZE bytes, written whole by vbc_get_info) and
  * added the I64 / I32 / BOOL eltypes, the sharded 2D handle and the *_ex sharded product; 3.3 added
- * VBC_CREATE_UPDATABLE and vbc_update_values (vbc_info unchanged). */
-#define VBC_VERSION 30300
+ * VBC_CREATE_UPDATABLE and vbc_update_values; 3.4 added VBC_CREATE_UPDATABLE_SHARDS and
+ * vbc_sharded_update_values (vbc_info unchanged by both). */
+#define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
 #ifdef __cplusplus
@@ -94,6 +95,17 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       stores 32-bit source indices: a val of more than 2^31 - 2 elements is
                                       refused (VBC_INVALID_ARG).  Create builds the layout on the host three
                                       times (once for the handle, twice to record the map). */
+
+#define VBC_CREATE_UPDATABLE_SHARDS 0x40u /* vbc1d_create_sharded / vbc2d_create_sharded only (with any flag they
+                                      accept; the single-GPU creates refuse it, VBC_INVALID_ARG): every shard is
+                                      created with VBC_CREATE_UPDATABLE (its map shows in the shard's
+                                      vbc_info.device_bytes, and each of the N shards pays the three host builds),
+                                      and the sharded handle keeps a value plan -- which elements of the whole
+                                      matrix's val each shard holds -- so that vbc_sharded_update_values can
+                                      rewrite all shards in place.  The flag changes no shard's layout, cut or x
+                                      span.  VBC_CREATE_UPDATABLE (0x20) itself stays refused by the sharded
+                                      creates, as in 3.3: callers of that version and a test rely on the refusal,
+                                      so the sharded capability has its own bit. */
 
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
@@ -299,6 +311,26 @@ VBC_API int vbc_sharded_mul(vbc_sharded *s, int trans, const void *x, int64_t nx
 VBC_API int vbc_sharded_mul_ex(vbc_sharded *s, int trans, const void *x, int x_dtype, int64_t incx, int64_t nx,
                                void *y, int y_dtype, int64_t incy, int64_t ny, double alpha, double beta, int mem,
                                void *stream, unsigned flags);
+
+/* vbc_update_values for a sharded handle created with VBC_CREATE_UPDATABLE_SHARDS: `val` is the WHOLE matrix's
+ * value array, in the order and with the length contract of create, of any vbc_dtype (converted in the shards'
+ * update kernels).  Every check happens before any work, so a refused call leaves every shard as it was:
+ * nval < ofs[L+1]-1 -> VBC_DIM_MISMATCH; a handle created without the flag -> VBC_INVALID_ARG; a float val on an
+ * integer handle or an unknown val_dtype -> VBC_UNSUPPORTED_DTYPE; a FAILED handle -> VBC_RCCL_ERROR.  Updates and
+ * products of one sharded handle are issued one at a time (the product lock).
+ *   mem = VBC_MEM_DEVICE: val lives on devices[0].  The whole update is ordered on `stream` without host
+ *     synchronisation: for VBC_SPLIT_ROWS one pack kernel permutes val into per-shard slices on devices[0] (for
+ *     VBC_SPLIT_STRIPES the slices are val's own); a shard on devices[0] runs its update kernel on its slice, a
+ *     shard on another device receives the slice's bytes (ncclSend / ncclRecv on the shard streams, which wait
+ *     for an event on `stream` and are joined back into it, as in a product) and runs the same kernel there.
+ *     Products enqueued on `stream` before the call see the old values, products enqueued after it the new ones.
+ *   mem = VBC_MEM_HOST: the host slices (packs) val per shard and runs each shard's host update; returns when
+ *     every shard is complete.  No RCCL.
+ * The staging (packed buffer, per-shard slice buffers) is allocated at create for the create-time val_dtype: an
+ * update with that or a narrower val_dtype allocates nothing; a wider one re-allocates it first, which
+ * synchronises the devices. */
+VBC_API int vbc_sharded_update_values(vbc_sharded *s, const void *val, int64_t nval, int val_dtype, int mem,
+                                      void *stream);
 
 VBC_API int vbc_sharded_destroy(vbc_sharded *s);
 VBC_API int vbc_sharded_count(const vbc_sharded *s, int *ngpus);

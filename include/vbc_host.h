@@ -91,6 +91,25 @@ VBC_API int vbcx_vbc_fill(int64_t m, int64_t n, int64_t U, int64_t W, const int6
 VBC_API int vbcx_transpose_pattern(int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval,
                            int64_t *rowptr, int64_t *colval);
 
+/* The value plan of a sharded handle (vbc.h VBC_CREATE_UPDATABLE_SHARDS): which elements of val each of the
+ * `ngpus` shards of vbc1d_create_sharded / vbc2d_create_sharded holds -- the function those creates build their
+ * shards with.  Matrix fields as vbc1d_create (pspl = NULL; K ignored) or vbc2d_create; compute_size = bytes of
+ * the compute eltype (4 / 8: the byte balance of the cuts); split = VBC_SPLIT_STRIPES or VBC_SPLIT_ROWS.
+ * Outputs (each may be NULL):
+ *   cuts[ngpus+1]       0-based ranges of the split dimension (columns / rows), as vbc_sharded_shard reports;
+ *   vbase[ngpus+1]      shard g holds vbase[g+1] - vbase[g] values: the slice [vbase[g], vbase[g+1]) of the packed
+ *                       order (shard 0's values, then shard 1's, ...); for the stripe split that is val's own
+ *                       order, shard g = val[vbase[g] : vbase[g+1]), and there are no runs;
+ *   run_begin[ngpus+1]  row split: shard g's runs are run_begin[g] .. run_begin[g+1]-1;
+ *   *nruns              number of runs (always written);
+ *   runs[3*nruns]       (src element, dst element, length) per run, 0-based, dst in packed order and ascending;
+ *                       kept blocks adjacent in val are one run.  Written only when run_capacity >= *nruns
+ *                       (call once with runs = NULL for the count). */
+VBC_API int vbcx_sharded_value_plan(int64_t m, int64_t n, int64_t K, const int64_t *pspl, int64_t L,
+                                    const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
+                                    int compute_size, int ngpus, int split, int64_t *cuts, int64_t *vbase,
+                                    int64_t *run_begin, int64_t *nruns, int64_t *runs, int64_t run_capacity);
+
 #ifdef __cplusplus
 }
 #endif

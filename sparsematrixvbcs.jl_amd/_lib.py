@@ -19,6 +19,7 @@ VBC_MEM_DEVICE, VBC_MEM_HOST = 0, 1
 VBC_CREATE_TRANSPOSED, VBC_CREATE_FORWARD, VBC_CREATE_MULTI, VBC_CREATE_SERIAL = 0x1, 0x2, 0x4, 0x8
 VBC_CREATE_MULTI_FORWARD = 0x10
 VBC_CREATE_UPDATABLE = 0x20
+VBC_CREATE_UPDATABLE_SHARDS = 0x40  # the sharded creates only (they refuse 0x20)
 VBC_VERSION_MAJOR = 3  # include/vbc.h VBC_VERSION / 10000: the vbc_info layout below is that version's
 VBC_INFO_SIZE = 152
 VBC_MUL_REFERENCE_QUIRKS = 0x1
@@ -31,10 +32,10 @@ ABI_SYMBOLS = (
     "vbc1d_create_ex", "vbc2d_create_ex", "vbc_csc_create_ex", "vbc_mul_ex", "vbc_mul_mat_ex",
     "vbc_get_info", "vbc_last_error", "vbc_version", "vbc_update_values",
     "vbc1d_create_sharded", "vbc2d_create_sharded", "vbc_sharded_mul", "vbc_sharded_mul_ex", "vbc_sharded_destroy",
-    "vbc_sharded_count", "vbc_sharded_shard", "vbc_sharded_split", "vbc_sharded_xspan",
+    "vbc_sharded_count", "vbc_sharded_shard", "vbc_sharded_split", "vbc_sharded_xspan", "vbc_sharded_update_values",
     "vbcx_partition_equi", "vbcx_partition_strict", "vbcx_partition_overlap",
     "vbcx_partition_dynamic", "vbcx_partition_dynamic_table", "vbcx_partition_block", "vbcx_1dvbc_count", "vbcx_1dvbc_fill", "vbcx_vbc_count",
-    "vbcx_vbc_fill", "vbcx_transpose_pattern",
+    "vbcx_vbc_fill", "vbcx_transpose_pattern", "vbcx_sharded_value_plan",
 )
 
 
@@ -115,6 +116,7 @@ def lib():
         L.vbc_sharded_mul.argtypes = [P, INT, P, I64, P, I64, D, D, INT, P, U]
         L.vbc_sharded_mul_ex.argtypes = [P, INT, P, INT, I64, I64, P, INT, I64, I64, D, D, INT, P, U]
         L.vbc_sharded_destroy.argtypes = [P]
+        L.vbc_sharded_update_values.argtypes = [P, P, I64, INT, INT, P]
         L.vbc_sharded_count.argtypes = [P, C.POINTER(INT)]
         L.vbc_sharded_split.argtypes = [P, C.POINTER(INT)]
         L.vbc_sharded_shard.argtypes = [P, INT, C.POINTER(P), C.POINTER(I64), C.POINTER(I64), C.POINTER(INT)]
@@ -135,6 +137,7 @@ def lib():
         L.vbcx_vbc_count.argtypes = [I64, I64, P, P, I64, P, I64, P, P, P]
         L.vbcx_vbc_fill.argtypes = [I64, I64, I64, I64, P, P, P, INT, I64, P, I64, P, P, P, P, P, I64]
         L.vbcx_transpose_pattern.argtypes = [I64, I64, P, P, P, P]
+        L.vbcx_sharded_value_plan.argtypes = [I64, I64, I64, P, I64, P, P, P, P, INT, INT, INT, P, P, P, P, P, I64]
         _lib = L
     return _lib
 

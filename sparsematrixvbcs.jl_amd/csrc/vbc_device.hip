@@ -3171,6 +3171,14 @@ static int create_updatable(vbc_handle **out, F &&create)
 }
 }  // extern "C++"
 
+// VBC_CREATE_UPDATABLE_SHARDS belongs to the sharded creates (vbc_sharded.cpp), which pass VBC_CREATE_UPDATABLE on
+// to their shards; the plain and *_ex creates end here.
+static int refuse_sharded_flag(vbc_handle **out)
+{
+    if (out) *out = nullptr;
+    return fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE_SHARDS is a flag of the sharded creates (single handle: VBC_CREATE_UPDATABLE)");
+}
+
 static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
                      const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
                      int64_t nval, int dtype, int device, unsigned flags)
@@ -3214,6 +3222,7 @@ int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, c
                  const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
                  int64_t nval, int dtype, int device, unsigned flags)
 {
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
     if (!(flags & VBC_CREATE_UPDATABLE))
         return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
@@ -3290,6 +3299,7 @@ int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, i
                  const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
                  int device, unsigned flags)
 {
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
     if (!(flags & VBC_CREATE_UPDATABLE))
         return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
@@ -3375,6 +3385,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
 int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                    const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
 {
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
     if (!(flags & VBC_CREATE_UPDATABLE)) return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
     // the tags go into an nzval-shaped array, before the column blocking below copies them into its stripes

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "vbc.h"
 
@@ -89,5 +90,26 @@ inline void host_store(const void *src, int cdt, int64_t n, void *dst, int dt, i
     }
     (void)cdt;
 }
+
+// The value plan of a sharded handle (vbc_sharded.cpp value_plan; vbc_host.h vbcx_sharded_value_plan): which
+// elements of the whole matrix's val each shard holds.  Packed order is shard 0's values, then shard 1's, ...;
+// shard g's slice is [vbase[g], vbase[g+1]).  Stripe split: the packed order is val's own (no runs).  Row split:
+// runs[rbeg[g] .. rbeg[g+1]) are shard g's, ascending in dst, covering its slice exactly once; blocks adjacent in
+// both val and the slice are one run.
+struct ValueRun {
+    int64_t src, dst, len;  // element offsets into val / the packed order
+};
+struct ValuePlan {
+    std::vector<int64_t> vbase, rbeg;  // ngpus + 1 each
+    std::vector<ValueRun> runs;
+    bool identity = true;              // every run has src == dst: the packed order is val's own
+};
+
+// vbc_pack.hip: one launch permutes val (raw elements of `vsz` bytes) into packed order.  rdst: the runs' dst
+// offsets plus a closing nval (nruns + 1, ascending); rsrc: their src offsets; tile_first[t]: the run that holds
+// destination element t * kPackTile (ntiles + 1 entries, the last one nruns - 1).  Device pointers of one device.
+constexpr int64_t kPackTile = 2048;  // destination elements per tile, whatever the element size
+int pack_launch(const int64_t *rdst, const int64_t *rsrc, const int64_t *tile_first, int64_t ntiles, int64_t nval,
+                const void *val, void *packed, int vsz, int cus, void *stream);
 
 }  // namespace vbc

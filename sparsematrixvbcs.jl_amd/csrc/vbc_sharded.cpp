@@ -42,6 +42,7 @@
 
 #include <cmath>
 
+#include "vbc_host.h"
 #include "vbc_internal.h"
 
 namespace vbc {  // vbc_generic.hip: strided eltype conversion kernels (vbc_mul_ex uses the same)
@@ -68,7 +69,19 @@ struct vbc_sharded {
     void *hx = nullptr, *hy = nullptr;  // root: staging of host / converted / strided operands
     hipEvent_t stage_ev = nullptr;   // recorded after the last product that used hx / hy
     bool stage_used = false;
-    std::mutex mu;                   // products are issued one at a time (collective order, buffers)
+    std::mutex mu;                   // products and value updates are issued one at a time (collective order, buffers)
+    // VBC_CREATE_UPDATABLE_SHARDS (vbc_sharded_update_values): the value plan and the staging of an update
+    bool upd = false;
+    vbc::ValuePlan vp;               // which source elements each shard holds (host copy: the VBC_MEM_HOST path)
+    int vsz_stage = 0;               // element size the staging below is sized for (the create-time val_dtype)
+    int cus = 256;                   // compute units of devices[0] (grid of the pack kernel)
+    void *d_plan = nullptr;          // root: run dst offsets (nruns + 1), run src offsets (nruns), per-tile first run
+    const int64_t *d_rdst = nullptr, *d_rsrc = nullptr, *d_tile = nullptr;
+    int64_t ntiles = 0;
+    void *d_packed = nullptr;        // root: val in packed order (row split with a non-identity plan)
+    std::vector<void *> vb;          // per shard on another device than the root's: its slice of the packed values
+    hipEvent_t pack_ev = nullptr;    // recorded after the last update that used d_packed
+    bool pack_used = false;
 };
 
 namespace {
@@ -173,6 +186,7 @@ void destroy_all(vbc_sharded *s)
     if (s->stage_ev) {
         DevGuard dg(s->dev[0]);
         (void)hipEventSynchronize(s->stage_ev);
+        if (s->pack_ev) (void)hipEventSynchronize(s->pack_ev);
     }
     for (ncclComm_t c : s->comm)
         if (c) (void)ncclCommDestroy(c);
@@ -187,7 +201,11 @@ void destroy_all(vbc_sharded *s)
             if (s->stage_ev) (void)hipEventDestroy(s->stage_ev);
             if (s->hx) (void)hipFree(s->hx);
             if (s->hy) (void)hipFree(s->hy);
+            if (s->pack_ev) (void)hipEventDestroy(s->pack_ev);
+            if (s->d_plan) (void)hipFree(s->d_plan);
+            if (s->d_packed) (void)hipFree(s->d_packed);
         }
+        if (g < s->vb.size() && s->vb[g]) (void)hipFree(s->vb[g]);
     }
     for (vbc_handle *h : s->h)
         if (h) (void)vbc_destroy(h);
@@ -550,6 +568,123 @@ int auto_split(const Fields &f, int csz, int N, unsigned flags)
     return (fw && !t) ? VBC_SPLIT_ROWS : VBC_SPLIT_STRIPES;
 }
 
+// The index arrays of one row shard (1-based, as create_shard takes them); Φ.spl is the whole matrix's.
+struct RowShard {
+    std::vector<int64_t> pg, og, ig;
+};
+
+// The value plan of a split (vbc_internal.h ValuePlan) and, shard by shard, what the shard is built from:
+// on_shard(g, rs) runs once per shard, after vp.vbase[g + 1] and the shard's runs are known -- rs = NULL for the
+// stripe split (the shard is the stripes [cuts[g], cuts[g+1]) and the slice val[vbase[g] : vbase[g+1])), the row
+// shard's index arrays otherwise (its values are its runs).  create_sharded builds the shards' handles in
+// on_shard and vbcx_sharded_value_plan reports vp, so the plan an update follows is the one the shards were
+// built from.
+template <typename OnShard>
+int value_plan(const Fields &f, const Plan &plan, int N, int split, vbc::ValuePlan &vp, OnShard &&on_shard)
+{
+    const int64_t L = f.L;
+    const std::vector<int64_t> &S = f.S, &P = f.P, &I = f.I, &O = f.O;
+    vp = vbc::ValuePlan();
+    if (split == VBC_SPLIT_STRIPES) {
+        vp.vbase.resize(N + 1);
+        vp.rbeg.assign(N + 1, 0);
+        for (int g = 0; g <= N; g++) vp.vbase[g] = O[plan.cuts[g]] - 1;
+        for (int g = 0; g < N; g++)
+            if (int st = on_shard(g, static_cast<const RowShard *>(nullptr))) return st;
+        return VBC_OK;
+    }
+    vp.vbase.assign(1, 0);
+    vp.rbeg.assign(1, 0);
+    for (int g = 0; g < N; g++) {
+        const int64_t k0 = plan.cuts[g], k1 = plan.cuts[g + 1];
+        RowShard rs;
+        rs.pg.resize(L + 1);
+        rs.og.resize(L + 1);
+        rs.pg[0] = rs.og[0] = 1;
+        int64_t dst = vp.vbase[g];
+        for (int64_t l = 0; l < L; l++) {
+            const int64_t w = S[l + 1] - S[l];
+            int64_t kept = 0, kept_vals = 0, off = O[l] - 1;  // running value offset inside the stripe
+            for (int64_t r = P[l] - 1; r < P[l + 1] - 1; r++) {
+                const int64_t bsz = f.u(I[r] - 1) * w;
+                if (I[r] > k0 && I[r] <= k1) {
+                    rs.ig.push_back(I[r] - k0);
+                    const bool open = (int64_t)vp.runs.size() > vp.rbeg[g];
+                    if (open && vp.runs.back().src + vp.runs.back().len == off) vp.runs.back().len += bsz;  // dst is contiguous
+                    else vp.runs.push_back({off, dst, bsz});
+                    dst += bsz;
+                    kept++;
+                    kept_vals += bsz;
+                }
+                off += bsz;
+            }
+            rs.pg[l + 1] = rs.pg[l] + kept;
+            rs.og[l + 1] = rs.og[l] + kept_vals;
+        }
+        vp.vbase.push_back(dst);
+        vp.rbeg.push_back((int64_t)vp.runs.size());
+        if (int st = on_shard(g, &rs)) return st;
+    }
+    for (const vbc::ValueRun &r : vp.runs) vp.identity = vp.identity && r.src == r.dst;
+    return VBC_OK;
+}
+
+// Device side of the value plan (VBC_CREATE_UPDATABLE_SHARDS): the run table and the packed buffer on the root
+// (row split, unless the plan is the identity), a slice buffer per shard on another device.  Sized for
+// elements of `vsz` bytes; called again by an update with a wider val_dtype (hipFree synchronises).
+int update_staging(vbc_sharded *s, int vsz)
+{
+    const int G = s->ngpus;
+    const vbc::ValuePlan &vp = s->vp;
+    const int64_t nval = vp.vbase[G];
+    {
+        DevGuard dg(s->dev[0]);
+        if (!dg.ok) return vbc::fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        if (!s->pack_ev) VBC_HIPS(hipEventCreateWithFlags(&s->pack_ev, hipEventDisableTiming));
+        if (!vp.identity && nval > 0) {
+            if (!s->d_plan) {
+                int cus = 0;
+                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->dev[0]) == hipSuccess && cus > 0)
+                    s->cus = cus;
+                const int64_t R = (int64_t)vp.runs.size(), T = (nval + vbc::kPackTile - 1) / vbc::kPackTile;
+                std::vector<int64_t> tab((size_t)(2 * R + 1 + T + 1));
+                int64_t *rdst = tab.data(), *rsrc = rdst + R + 1, *tile = rsrc + R;
+                for (int64_t r = 0; r < R; r++) {
+                    rdst[r] = vp.runs[r].dst;
+                    rsrc[r] = vp.runs[r].src;
+                }
+                rdst[R] = nval;
+                for (int64_t t = 0, r = 0; t < T; t++) {  // the run that holds element t * kPackTile
+                    while (rdst[r + 1] <= t * vbc::kPackTile) r++;
+                    tile[t] = r;
+                }
+                tile[T] = R - 1;
+                VBC_HIPS(hipMalloc(&s->d_plan, tab.size() * 8));
+                VBC_HIPS(hipMemcpy(s->d_plan, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+                s->d_rdst = static_cast<const int64_t *>(s->d_plan);
+                s->d_rsrc = s->d_rdst + R + 1;
+                s->d_tile = s->d_rsrc + R;
+                s->ntiles = T;
+            }
+            if (s->d_packed) VBC_HIPS(hipFree(s->d_packed));
+            s->d_packed = nullptr;
+            VBC_HIPS(hipMalloc(&s->d_packed, ((size_t)nval * vsz + 15) & ~size_t(15)));
+        }
+    }
+    s->vb.resize(G, nullptr);
+    for (int g = 1; g < G && !s->comm.empty(); g++) {
+        const int64_t cnt = vp.vbase[g + 1] - vp.vbase[g];
+        if (cnt == 0) continue;
+        DevGuard dg(s->dev[g]);
+        if (!dg.ok) return vbc::fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        if (s->vb[g]) VBC_HIPS(hipFree(s->vb[g]));
+        s->vb[g] = nullptr;
+        VBC_HIPS(hipMalloc(&s->vb[g], (size_t)cnt * vsz));
+    }
+    s->vsz_stage = vsz;
+    return VBC_OK;
+}
+
 int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *types, int ngpus, const int *devices,
                    int split, unsigned flags)
 {
@@ -557,8 +692,13 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
     *out = nullptr;
     if (!types) return vbc::fail(VBC_INVALID_ARG, "NULL vbc_types");
     if (ngpus < 1 || !devices) return vbc::fail(VBC_INVALID_ARG, "ngpus must be >= 1 with a device list");
-    if (flags & VBC_CREATE_UPDATABLE)  // the shards are built from re-sliced values: their maps would need composing
-        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE is not supported on sharded handles");
+    if (flags & VBC_CREATE_UPDATABLE)  // 3.3 callers rely on this refusal; the sharded flag is its own bit
+        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE is not supported on sharded handles "
+                                          "(pass VBC_CREATE_UPDATABLE_SHARDS)");
+    // VBC_CREATE_UPDATABLE_SHARDS: every shard keeps its own value map; the value plan below says which of the
+    // whole matrix's values it holds
+    const bool upd = (flags & VBC_CREATE_UPDATABLE_SHARDS) != 0;
+    const unsigned sflags = upd ? (flags & ~VBC_CREATE_UPDATABLE_SHARDS) | VBC_CREATE_UPDATABLE : flags;
     if (split != VBC_SPLIT_STRIPES && split != VBC_SPLIT_ROWS && split != VBC_SPLIT_AUTO)
         return vbc::fail(VBC_INVALID_ARG, "split must be VBC_SPLIT_STRIPES, VBC_SPLIT_ROWS or VBC_SPLIT_AUTO");
     int count = 0;
@@ -594,58 +734,41 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
     Plan plan = plan_split(f, csz, ngpus, split);
     s->xlo = plan.xlo;
     s->xhi = plan.xhi;
-    if (split == VBC_SPLIT_STRIPES) {
-        const std::vector<int64_t> &lc = plan.cuts;
-        s->cut.resize(ngpus + 1);
-        for (int g = 0; g <= ngpus; g++) s->cut[g] = S[lc[g]] - 1;  // column ranges
-        for (int g = 0; g < ngpus; g++) {
-            const int64_t a = lc[g], b = lc[g + 1], Lg = b - a;
+    s->cut.resize(ngpus + 1);
+    for (int g = 0; g <= ngpus; g++) {  // column ranges / row ranges
+        const int64_t c = plan.cuts[g];
+        s->cut[g] = split == VBC_SPLIT_STRIPES ? S[c] - 1 : f.is2d ? f.PS[c] - 1 : c;
+    }
+    vbc::ValuePlan vp;
+    int st = value_plan(f, plan, ngpus, split, vp, [&](int g, const RowShard *rs) -> int {
+        if (!rs) {  // stripes [a, b)
+            const int64_t a = plan.cuts[g], b = plan.cuts[g + 1], Lg = b - a;
             std::vector<int64_t> sg(Lg + 1), pg(Lg + 1), og(Lg + 1);
             for (int64_t l = 0; l <= Lg; l++) {
                 sg[l] = S[a + l] - (S[a] - 1);
                 pg[l] = P[a + l] - (P[a] - 1);
                 og[l] = O[a + l] - (O[a] - 1);
             }
-            int st = create_shard(f, &s->h[g], m, S[b] - S[a], f.K, f.PS.data(), Lg, sg.data(), pg.data(),
-                                  I.data() + (P[a] - 1), og.data(), V + (O[a] - 1) * vsz, &t64, devices[g], flags);
-            if (st) { destroy_all(s); return st; }
+            return create_shard(f, &s->h[g], m, S[b] - S[a], f.K, f.PS.data(), Lg, sg.data(), pg.data(),
+                                I.data() + (P[a] - 1), og.data(), V + vp.vbase[g] * vsz, &t64, devices[g], sflags);
         }
-    } else {
-        const std::vector<int64_t> &kc = plan.cuts;  // block-row ranges
-        s->cut.resize(ngpus + 1);
-        for (int g = 0; g <= ngpus; g++) s->cut[g] = f.is2d ? f.PS[kc[g]] - 1 : kc[g];  // row ranges
-        for (int g = 0; g < ngpus; g++) {
-            const int64_t k0 = kc[g], k1 = kc[g + 1];
-            std::vector<int64_t> pg(L + 1), og(L + 1), ig, psg;
-            std::vector<char> vg;
-            pg[0] = og[0] = 1;
-            for (int64_t l = 0; l < L; l++) {
-                const int64_t w = S[l + 1] - S[l];
-                int64_t kept = 0, kept_vals = 0, off = O[l] - 1;  // running value offset inside the stripe
-                for (int64_t r = P[l] - 1; r < P[l + 1] - 1; r++) {
-                    const int64_t bsz = f.u(I[r] - 1) * w;
-                    if (I[r] > k0 && I[r] <= k1) {
-                        ig.push_back(I[r] - k0);
-                        const char *src = V + off * vsz;
-                        vg.insert(vg.end(), src, src + bsz * vsz);
-                        kept++;
-                        kept_vals += bsz;
-                    }
-                    off += bsz;
-                }
-                pg[l + 1] = pg[l] + kept;
-                og[l + 1] = og[l] + kept_vals;
-            }
-            if (f.is2d) {
-                psg.resize(k1 - k0 + 1);
-                for (int64_t k = k0; k <= k1; k++) psg[k - k0] = f.PS[k] - (f.PS[k0] - 1);
-            }
-            int st = create_shard(f, &s->h[g], s->cut[g + 1] - s->cut[g], n, k1 - k0, psg.data(), L, S.data(),
-                                  pg.data(), ig.empty() ? nullptr : ig.data(), og.data(),
-                                  vg.empty() ? nullptr : vg.data(), &t64, devices[g], flags);
-            if (st) { destroy_all(s); return st; }
+        // block rows (k0, k1] of every stripe: the values are the shard's runs, copied in packed order
+        const int64_t k0 = plan.cuts[g], k1 = plan.cuts[g + 1];
+        std::vector<char> vg((size_t)(vp.vbase[g + 1] - vp.vbase[g]) * vsz);
+        for (int64_t r = vp.rbeg[g]; r < vp.rbeg[g + 1]; r++) {
+            const vbc::ValueRun &run = vp.runs[r];
+            std::memcpy(vg.data() + (run.dst - vp.vbase[g]) * vsz, V + run.src * vsz, (size_t)run.len * vsz);
         }
-    }
+        std::vector<int64_t> psg;
+        if (f.is2d) {
+            psg.resize(k1 - k0 + 1);
+            for (int64_t k = k0; k <= k1; k++) psg[k - k0] = f.PS[k] - (f.PS[k0] - 1);
+        }
+        return create_shard(f, &s->h[g], s->cut[g + 1] - s->cut[g], n, k1 - k0, psg.data(), L, S.data(), rs->pg.data(),
+                            rs->ig.empty() ? nullptr : rs->ig.data(), rs->og.data(), vg.empty() ? nullptr : vg.data(),
+                            &t64, devices[g], sflags);
+    });
+    if (st) { destroy_all(s); return st; }
 
     // streams, events, exchange buffers, communicators
     const int64_t big = std::max<int64_t>(std::max(m, n), 1);
@@ -682,12 +805,115 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
             return nccl_fail(r, "ncclCommInitAll");
         }
     }
+    if (upd) {  // every buffer an update with the create-time val_dtype needs
+        s->vp = std::move(vp);
+        s->upd = true;
+        if (int st2 = update_staging(s, vsz)) { destroy_all(s); return st2; }
+    }
     *out = s;
     return VBC_OK;
 }
 
 bool is_float(int dt) { return dt == VBC_F64 || dt == VBC_F32; }
 bool known_dtype(int dt) { return dt >= VBC_F64 && dt <= VBC_BOOL; }
+
+// vbc_sharded_update_values, device val on the root, everything ordered on the root stream s0: the pack (row
+// split), then per shard its update kernel on its slice -- straight from the packed values on the root's
+// device, after an ncclSend / ncclRecv of the slice's bytes on another one (the fork / join of mul_device).
+int update_device(vbc_sharded *s, const char *val, int val_dtype, hipStream_t s0, bool *issued)
+{
+    const int G = s->ngpus;
+    const vbc::ValuePlan &vp = s->vp;
+    const int64_t vsz = vbc::elem_size(val_dtype), nval = vp.vbase[G];
+    auto cnt = [&](int g) { return vp.vbase[g + 1] - vp.vbase[g]; };
+    const char *packed = val;
+    bool capturing = false;
+    {
+        DevGuard dg(s->dev[0]);
+        if (!dg.ok) return vbc::fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        if (s->d_packed) {
+            // the packed buffer is shared by all updates: one on another stream waits for the previous one.  Not
+            // while s0 is being captured into a HIP graph (the event would belong to the capture): the graph's
+            // own order holds there, and its owner orders replays against updates on other streams.
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s0, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+            capturing = cs != hipStreamCaptureStatusNone;
+            if (s->pack_used && !capturing) VBC_HIPS(hipStreamWaitEvent(s0, s->pack_ev, 0));
+            if (int st = vbc::pack_launch(s->d_rdst, s->d_rsrc, s->d_tile, s->ntiles, nval, val, s->d_packed, (int)vsz,
+                                          s->cus, s0))
+                return st;
+            packed = static_cast<const char *>(s->d_packed);
+        }
+    }
+    const bool remote = !s->comm.empty() && G > 1;
+    if (remote) {
+        {
+            DevGuard dg(s->dev[0]);
+            VBC_HIPS(hipEventRecord(s->start, s0));
+        }
+        for (int g = 1; g < G; g++) {
+            DevGuard dg(s->dev[g]);
+            VBC_HIPS(hipStreamWaitEvent(s->st[g], s->start, 0));
+        }
+        *issued = true;
+        NcclGroup grp;
+        for (int g = 1; g < G && grp.ok(); g++) {
+            if (cnt(g) == 0) continue;
+            grp.note(ncclSend(packed + vp.vbase[g] * vsz, (size_t)(cnt(g) * vsz), ncclUint8, g, s->comm[0], s0),
+                     "ncclSend(val slice)");
+            if (grp.ok())
+                grp.note(ncclRecv(s->vb[g], (size_t)(cnt(g) * vsz), ncclUint8, 0, s->comm[g], s->st[g]),
+                         "ncclRecv(val slice)");
+        }
+        if (int st = grp.end()) return st;
+    }
+    for (int g = 0; g < G; g++) {
+        if (cnt(g) == 0) continue;
+        const bool here = g == 0 || !remote;
+        if (int st = vbc_update_values(s->h[g], here ? (const void *)(packed + vp.vbase[g] * vsz) : s->vb[g], cnt(g),
+                                       val_dtype, VBC_MEM_DEVICE, here ? s0 : s->st[g]))
+            return st;
+    }
+    for (int g = 1; g < G && remote; g++) {
+        {
+            DevGuard dg(s->dev[g]);
+            VBC_HIPS(hipEventRecord(s->done[g], s->st[g]));
+        }
+        DevGuard dg(s->dev[0]);
+        VBC_HIPS(hipStreamWaitEvent(s0, s->done[g], 0));
+    }
+    if (s->d_packed && !capturing) {
+        DevGuard dg(s->dev[0]);
+        VBC_HIPS(hipEventRecord(s->pack_ev, s0));
+        s->pack_used = true;
+    }
+    return VBC_OK;
+}
+
+// Host val: sliced (stripe split) or packed shard by shard (row split) on the host, each shard's own host update
+// (which returns when the shard is complete).  No RCCL.
+int update_host(vbc_sharded *s, const char *val, int val_dtype)
+{
+    const vbc::ValuePlan &vp = s->vp;
+    const int64_t vsz = vbc::elem_size(val_dtype);
+    std::vector<char> buf;
+    for (int g = 0; g < s->ngpus; g++) {
+        const int64_t cnt = vp.vbase[g + 1] - vp.vbase[g];
+        if (cnt == 0) continue;
+        const char *src = val + vp.vbase[g] * vsz;
+        if (!vp.identity && s->split == VBC_SPLIT_ROWS) {
+            buf.resize((size_t)(cnt * vsz));
+            for (int64_t r = vp.rbeg[g]; r < vp.rbeg[g + 1]; r++)
+                std::memcpy(buf.data() + (vp.runs[r].dst - vp.vbase[g]) * vsz, val + vp.runs[r].src * vsz,
+                            (size_t)(vp.runs[r].len * vsz));
+            src = buf.data();
+        }
+        DevGuard dg(s->dev[g]);
+        if (!dg.ok) return vbc::fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        if (int st = vbc_update_values(s->h[g], src, cnt, val_dtype, VBC_MEM_HOST, nullptr)) return st;
+    }
+    return VBC_OK;
+}
 
 }  // namespace
 
@@ -786,6 +1012,73 @@ int vbc_sharded_mul(vbc_sharded *s, int trans, const void *x, int64_t nx, void *
         return mul_checked(s, trans, static_cast<const char *>(x), nx, static_cast<char *>(y), ny, alpha, beta,
                            (hipStream_t)stream);
     return mul_host(s, trans, x, nx, y, ny, alpha, beta);
+}
+
+int vbc_sharded_update_values(vbc_sharded *s, const void *val, int64_t nval, int val_dtype, int mem, void *stream)
+{
+    if (!s) return fail(VBC_INVALID_ARG, "NULL handle");
+    if (s->failed)
+        return fail(VBC_RCCL_ERROR, "sharded handle is FAILED (an earlier product or update failed mid-exchange); "
+                                    "destroy and re-create it");
+    if (!s->upd) return fail(VBC_INVALID_ARG, "sharded handle created without VBC_CREATE_UPDATABLE_SHARDS");
+    if (!known_dtype(val_dtype)) return fail(VBC_UNSUPPORTED_DTYPE, "unknown val_dtype");
+    if (s->cdt == VBC_I64 && is_float(val_dtype))
+        return fail(VBC_UNSUPPORTED_DTYPE, "floating-point values on an integer handle (InexactError)");
+    const int64_t need = s->vp.vbase[s->ngpus];
+    if (nval < need) return fail(VBC_DIM_MISMATCH, "DimensionMismatch: val shorter than at create");
+    if (need > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
+    if (mem != VBC_MEM_DEVICE && mem != VBC_MEM_HOST)
+        return fail(VBC_INVALID_ARG, "mem must be VBC_MEM_DEVICE or VBC_MEM_HOST");
+    if (need == 0) return VBC_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (mem == VBC_MEM_HOST) return update_host(s, static_cast<const char *>(val), val_dtype);
+    if (vbc::elem_size(val_dtype) > s->vsz_stage)  // a wider val_dtype than at create: the staging grows (synchronises)
+        if (int st = update_staging(s, vbc::elem_size(val_dtype))) return st;
+    bool issued = false;
+    const int st = update_device(s, static_cast<const char *>(val), val_dtype, (hipStream_t)stream, &issued);
+    if (st != VBC_OK && issued) s->failed = true;
+    return st;
+}
+
+int vbcx_sharded_value_plan(int64_t m, int64_t n, int64_t K, const int64_t *pspl, int64_t L, const int64_t *spl,
+                            const int64_t *pos, const int64_t *idx, const int64_t *ofs, int compute_size, int ngpus,
+                            int split, int64_t *cuts, int64_t *vbase, int64_t *run_begin, int64_t *nruns,
+                            int64_t *runs, int64_t run_capacity)
+{
+    if (L < 0 || m < 0 || n < 0 || !spl || !pos || !ofs || !nruns) return fail(VBC_INVALID_ARG, "bad stripe arrays");
+    if (ngpus < 1) return fail(VBC_INVALID_ARG, "ngpus must be >= 1");
+    if (split != VBC_SPLIT_STRIPES && split != VBC_SPLIT_ROWS)
+        return fail(VBC_INVALID_ARG, "split must be VBC_SPLIT_STRIPES or VBC_SPLIT_ROWS");
+    if (compute_size != 4 && compute_size != 8) return fail(VBC_INVALID_ARG, "compute_size must be 4 or 8");
+    Fields f;
+    f.is2d = pspl != nullptr;
+    if (f.is2d && K < 0) return fail(VBC_INVALID_ARG, "bad partition arrays");
+    f.m = m; f.n = n; f.K = f.is2d ? K : m; f.L = L;
+    if (f.is2d) f.PS = as64(pspl, 64, K + 1);
+    f.S = as64(spl, 64, L + 1);
+    f.P = as64(pos, 64, L + 1);
+    f.O = as64(ofs, 64, L + 1);
+    const int64_t q = f.P[L] - 1;
+    if (f.P[0] != 1 || q < 0 || (q > 0 && !idx)) return fail(VBC_INVALID_ARG, "bad pos");
+    f.I = as64(idx, 64, q);
+    if (int st = validate(f)) return st;
+    const Plan plan = plan_split(f, compute_size, ngpus, split);
+    vbc::ValuePlan vp;
+    if (int st = value_plan(f, plan, ngpus, split, vp, [](int, const RowShard *) { return (int)VBC_OK; })) return st;
+    for (int g = 0; g <= ngpus; g++) {
+        const int64_t c = plan.cuts[g];
+        if (cuts) cuts[g] = split == VBC_SPLIT_STRIPES ? f.S[c] - 1 : f.is2d ? f.PS[c] - 1 : c;
+        if (vbase) vbase[g] = vp.vbase[g];
+        if (run_begin) run_begin[g] = vp.rbeg[g];
+    }
+    *nruns = (int64_t)vp.runs.size();
+    if (runs && run_capacity >= *nruns)
+        for (int64_t r = 0; r < *nruns; r++) {
+            runs[3 * r] = vp.runs[r].src;
+            runs[3 * r + 1] = vp.runs[r].dst;
+            runs[3 * r + 2] = vp.runs[r].len;
+        }
+    return VBC_OK;
 }
 
 int vbc_sharded_mul_ex(vbc_sharded *s, int trans, const void *x, int x_dtype, int64_t incx, int64_t nx, void *y,

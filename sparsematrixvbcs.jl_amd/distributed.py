@@ -209,7 +209,7 @@ class ShardedSparseMatrix1DVBC:
     per rank.  See the module docstring for the two splits and which product needs a collective."""
 
     def __init__(self, B, rank, world, group=None, local_mul=None, device=None, split="stripes", comm="device",
-                 directions="tf"):
+                 directions="tf", updatable=False):
         if split == "auto":  # by the cost model: predicted kernel + collective time of the products to run
             split = choose_split(B, world, directions)
         if split not in ("stripes", "rows"):
@@ -231,12 +231,63 @@ class ShardedSparseMatrix1DVBC:
             self.row0 = int(self.cuts[rank])
             self.local, self.col0 = trim_stripes(row_shard(B, self.row0, int(self.cuts[rank + 1])))
         self.m_local, self.n_local = self.local.m, self.local.n
+        self.updatable = bool(updatable)
+        if self.updatable:  # before the first product: the local handles are created with the value map
+            self.local.updatable = True
+            self.val_index = self._value_index(B)
+            self._val_index_dev = None
         self.col_splits = self.splits if split == "stripes" else None  # (round-1 name)
         if local_mul is None:
             from .multiply import mul_
             local_mul = mul_
         self._product = local_mul  # mul!(y, op, x, α, β) on this rank's handle
         self.device = device
+
+    # --- value updates -------------------------------------------------------------------------
+    def _value_index(self, B):
+        """Which elements of B.val this rank's local matrix stores, in its order: the shard chain run on a copy
+        of B whose val holds the tag i + 1 in element i (the chain only copies values).  A slice for
+        the stripe split (contiguous), an int64 index array for the row split."""
+        nval = int(B.ofs[-1]) - 1
+        tags = np.zeros(len(B.val), np.int64)
+        tags[:nval] = np.arange(1, nval + 1)
+        Bt = SparseMatrix1DVBC(B.W, B.m, B.n, B.Phi, B.pos, B.idx, B.ofs, tags)
+        if self.split == "stripes":
+            sh, _ = shard(Bt, int(self.cuts[self.rank]), int(self.cuts[self.rank + 1]))
+            loc, _ = rebase_rows(sh)
+        else:
+            loc, _ = trim_stripes(row_shard(Bt, self.row0, int(self.cuts[self.rank + 1])))
+        nv = int(loc.ofs[-1]) - 1
+        index = loc.val[:nv] - 1
+        assert nv == int(self.local.ofs[-1]) - 1 and (index >= 0).all()
+        if self.split == "stripes":
+            lo = int(index[0]) if nv else 0
+            assert np.array_equal(index, np.arange(lo, lo + nv))
+            return slice(lo, lo + nv)
+        return index
+
+    def update_values(self, val_global, stream=None):
+        """New values for the same pattern: `val_global` is the WHOLE matrix's val (numpy, or a tensor on this
+        rank's device), of which this rank takes its own elements (`val_index`) and updates its local matrix in
+        place (SparseMatrix1DVBC.update_values).  Needs updatable=True.  No collective runs."""
+        from . import _lib as _L
+        if not self.updatable:
+            raise _L.ArgumentError("update_values needs ShardedSparseMatrix1DVBC(..., updatable=True)")
+        if len(val_global.shape) != 1:
+            raise _L.ArgumentError("val must be a vector")
+        need = self.val_index.stop if isinstance(self.val_index, slice) else \
+            (int(self.val_index.max()) + 1 if len(self.val_index) else 0)
+        if val_global.shape[0] < need:
+            raise _L.DimensionMismatch(f"val has {val_global.shape[0]} elements, this rank reads up to {need}")
+        if isinstance(val_global, np.ndarray) or isinstance(self.val_index, slice):
+            mine = val_global[self.val_index]
+        else:
+            import torch
+            if self._val_index_dev is None or self._val_index_dev.device != val_global.device:
+                self._val_index_dev = torch.from_numpy(self.val_index).to(val_global.device)
+            mine = val_global.index_select(0, self._val_index_dev)
+        self.local.update_values(mine if isinstance(mine, np.ndarray) else mine.contiguous(), stream)
+        return self
 
     # --- collectives ----------------------------------------------------------------------------
     def _all_reduce(self, t):
@@ -353,7 +404,8 @@ class MultiGPUSparseMatrix1DVBC:
     Like the single-GPU mul_, x / y may be any strided vectors of any supported eltype (converted to
     the handle's compute eltype, multiply_1DVBC.jl:9,85,102): vbc_sharded_mul_ex carries them."""
 
-    def __init__(self, B, devices=(0,), split="stripes", transposed=True, forward=True, serial=False):
+    def __init__(self, B, devices=(0,), split="stripes", transposed=True, forward=True, serial=False,
+                 updatable=False):
         import ctypes as C
         from . import _lib as _L
         if split not in ("stripes", "rows", "auto"):
@@ -365,7 +417,9 @@ class MultiGPUSparseMatrix1DVBC:
         self.is2d = hasattr(B, "Pi")
         self.devices = [int(d) for d in devices]
         flags = ((_L.VBC_CREATE_TRANSPOSED if transposed else 0) | (_L.VBC_CREATE_FORWARD if forward else 0)
-                 | (_L.VBC_CREATE_SERIAL if serial else 0))
+                 | (_L.VBC_CREATE_SERIAL if serial else 0) | (_L.VBC_CREATE_UPDATABLE_SHARDS if updatable else 0))
+        self.updatable = bool(updatable)
+        self._nval = int(B.ofs[-1]) - 1
         t = _L.vbc_types(_L.dtype_code(B.val.dtype), 64, _L.compute_code(B.val.dtype), 0)
         devs = (C.c_int * len(self.devices))(*self.devices)
         h = C.c_void_p()
@@ -455,6 +509,40 @@ class MultiGPUSparseMatrix1DVBC:
                                              _stride(y), ny, float(alpha), float(beta), mem, stream, flags),
                  "mul! (sharded)")
         return y
+
+    def update_values(self, val, stream=None):
+        """New values for the same pattern (vbc.h vbc_sharded_update_values): `val` is the whole matrix's value
+        array, ordered like B.val and at least ofs[L+1]-1 long -- a numpy array, or a contiguous tensor on
+        devices[0], enqueued on `stream` (default: torch's current stream of that device) without
+        synchronising.  Every shard is rewritten in place; needs updatable=True."""
+        from . import _lib as _L
+        if not self.updatable:
+            raise _L.ArgumentError("update_values needs MultiGPUSparseMatrix1DVBC(..., updatable=True)")
+        if len(val.shape) != 1:
+            raise _L.ArgumentError("val must be a vector")
+        if val.shape[0] < self._nval:
+            raise _L.DimensionMismatch(f"val has {val.shape[0]} elements, the pattern stores {self._nval}")
+        code = _L.dtype_code(val.dtype)
+        if self.dtype.kind != "f" and code in (_L.VBC_F64, _L.VBC_F32):
+            raise _L.UnsupportedDtype("floating-point values for an integer matrix (InexactError)")
+        if type(val).__module__.startswith("torch"):
+            if not val.is_cuda or val.device.index != self.devices[0]:
+                raise _L.ArgumentError(f"a torch val must live on devices[0] = cuda:{self.devices[0]} "
+                                       "(pass a numpy array for host values)")
+            if not val.is_contiguous():
+                raise _L.ArgumentError("val must be contiguous")
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(val.device).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            st = _L.lib().vbc_sharded_update_values(self._h, val.data_ptr(), val.shape[0], code, _L.VBC_MEM_DEVICE,
+                                                    stream)
+        else:
+            host = np.ascontiguousarray(val)
+            st = _L.lib().vbc_sharded_update_values(self._h, host.ctypes.data, len(host), code, _L.VBC_MEM_HOST, None)
+        _L.check(st, "update_values (sharded)")
+        return self
 
     def release(self):
         from . import _lib as _L

@@ -243,7 +243,7 @@ Base.:*(adjA::AdjOrTransHIP, x::StridedVector{T}) where {T} =
 TrSpMV!(y::StridedVector, A::HIPSparseMatrixCSC, x::StridedVector) = _mul!(y, A, true, x, true, false)
 
 """
-    HIPShardedSparseMatrix(B; devices=0:7, split=:stripes, serial=false)
+    HIPShardedSparseMatrix(B; devices=0:7, split=:stripes, serial=false, updatable=false)
 
 `B` (a SparseMatrix1DVBC or a SparseMatrixVBC) split over several GPUs of the node by byte-balanced
 stripe (`split=:stripes`, the block rows of A when B stores Aᵀ) or row (`split=:rows`; Π's block rows
@@ -252,30 +252,35 @@ for a SparseMatrixVBC) ranges, one handle per GPU, RCCL over xGMI for the exchan
 (multiply_1DVBC.jl:169-177, multiply_VBC.jl:182-189).  Computes in Tv (integers and Bool in exact
 Int64); host StridedVectors of any supported eltype (x converted like multiply_1DVBC.jl:102) or, with
 AMDGPU, ROCVectors on `devices[1]`.  `serial=true` keeps the reference's serial per-stripe summation
-order in every shard (VBC_CREATE_SERIAL).
+order in every shard (VBC_CREATE_SERIAL).  `updatable=true` (VBC_CREATE_UPDATABLE_SHARDS) lets
+`update_values!(Bs, val)` rewrite every shard's stored values in place.
 """
 mutable struct HIPShardedSparseMatrix{M}
     host::M
     handle::Ptr{Cvoid}
     compute::Cint
+    updatable::Bool
 end
+HIPShardedSparseMatrix(host, handle, compute) = HIPShardedSparseMatrix(host, handle, compute, false)
 const HIPShardedSparseMatrix1DVBC = HIPShardedSparseMatrix  # round-2 name
 
 const VBC_CREATE_SERIAL = Cuint(8)
 const VBC_CREATE_UPDATABLE = Cuint(0x20)
+const VBC_CREATE_UPDATABLE_SHARDS = Cuint(0x40)  # the sharded creates only (they refuse 0x20)
 
 _split_code(split) = split === :stripes ? VBC_SPLIT_STRIPES : split === :rows ? VBC_SPLIT_ROWS : VBC_SPLIT_AUTO
 
-function _sharded_flags(split, forward, transposed, serial)
+function _sharded_flags(split, forward, transposed, serial, updatable=false)
     split in (:stripes, :rows, :auto) || throw(ArgumentError("split must be :stripes, :rows or :auto"))
     return (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
-           (serial ? VBC_CREATE_SERIAL : Cuint(0))
+           (serial ? VBC_CREATE_SERIAL : Cuint(0)) | (updatable ? VBC_CREATE_UPDATABLE_SHARDS : Cuint(0))
 end
 _default_compute(::Type{Tv}) where {Tv} = Tv <: AbstractFloat ? compute_dtype(Tv) : VBC_I64
 
 function HIPShardedSparseMatrix(B::SparseMatrix1DVBC{W, Tv, Ti}; devices=0:7, split::Symbol=:stripes,
-                                forward::Bool=true, transposed::Bool=true, serial::Bool=false) where {W, Tv, Ti}
-    flags = _sharded_flags(split, forward, transposed, serial)
+                                forward::Bool=true, transposed::Bool=true, serial::Bool=false,
+                                updatable::Bool=false) where {W, Tv, Ti}
+    flags = _sharded_flags(split, forward, transposed, serial, updatable)
     devs = Cint.(collect(devices))
     h = Ref{Ptr{Cvoid}}(C_NULL)
     cdt = _default_compute(Tv)
@@ -285,14 +290,15 @@ function HIPShardedSparseMatrix(B::SparseMatrix1DVBC{W, Tv, Ti}; devices=0:7, sp
          Ptr{VbcTypes}, Cint, Ptr{Cint}, Cint, Cuint),
         h, B.m, B.n, W, length(B.Φ), B.Φ.spl, B.pos, B.idx, B.ofs, B.val, length(B.val), t, length(devs), devs,
         _split_code(split), flags))
-    M = HIPShardedSparseMatrix(B, h[], cdt)
+    M = HIPShardedSparseMatrix(B, h[], cdt, updatable)
     finalizer(M -> ccall((:vbc_sharded_destroy, libvbc), Cint, (Ptr{Cvoid},), M.handle), M)
     return M
 end
 
 function HIPShardedSparseMatrix(B::SparseMatrixVBC{U, W, Tv, Ti}; devices=0:7, split::Symbol=:stripes,
-                                forward::Bool=true, transposed::Bool=true, serial::Bool=false) where {U, W, Tv, Ti}
-    flags = _sharded_flags(split, forward, transposed, serial)
+                                forward::Bool=true, transposed::Bool=true, serial::Bool=false,
+                                updatable::Bool=false) where {U, W, Tv, Ti}
+    flags = _sharded_flags(split, forward, transposed, serial, updatable)
     devs = Cint.(collect(devices))
     h = Ref{Ptr{Cvoid}}(C_NULL)
     cdt = _default_compute(Tv)
@@ -302,12 +308,30 @@ function HIPShardedSparseMatrix(B::SparseMatrixVBC{U, W, Tv, Ti}; devices=0:7, s
          Ptr{Cvoid}, Int64, Ptr{VbcTypes}, Cint, Ptr{Cint}, Cint, Cuint),
         h, B.m, B.n, U, W, length(B.Π), B.Π.spl, length(B.Φ), B.Φ.spl, B.pos, B.idx, B.ofs, B.val, length(B.val), t,
         length(devs), devs, _split_code(split), flags))
-    M = HIPShardedSparseMatrix(B, h[], cdt)
+    M = HIPShardedSparseMatrix(B, h[], cdt, updatable)
     finalizer(M -> ccall((:vbc_sharded_destroy, libvbc), Cint, (Ptr{Cvoid},), M.handle), M)
     return M
 end
 
 Base.size(A::HIPShardedSparseMatrix) = size(A.host)
+
+"""
+    update_values!(A::HIPShardedSparseMatrix, val::StridedVector)
+
+New values for the same pattern on every shard (vbc_sharded_update_values): `val` is the whole matrix's value
+array, ordered like `A.host.val`.  `A` must have been made with `updatable=true` (ArgumentError otherwise).
+Returns when every shard is complete.
+"""
+function update_values!(A::HIPShardedSparseMatrix, val::StridedVector{Tn}) where {Tn}
+    A.updatable || throw(ArgumentError("update_values! needs updatable=true"))
+    stride(val, 1) == 1 || throw(ArgumentError("val must be contiguous"))
+    GC.@preserve val check(ccall((:vbc_sharded_update_values, libvbc), Cint,
+        (Ptr{Cvoid}, Ptr{Tn}, Int64, Cint, Cint, Ptr{Cvoid}),
+        A.handle, pointer(val), length(val), vbc_dtype(Tn), VBC_MEM_HOST, C_NULL))
+    hv = A.host.val
+    copyto!(hv, 1, val, 1, min(length(hv), length(val)))
+    return A
+end
 
 "The split a sharded matrix uses (:stripes or :rows; what split = :auto chose by the cost model, DESIGN.md §7)."
 function split_kind(A::HIPShardedSparseMatrix)

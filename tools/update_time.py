@@ -11,6 +11,14 @@ the map's size, (device_bytes with the flag - device_bytes without) / 4.  (a) is
 8 TB/s that traffic reaches.  One JSON line; --out writes it to a file as well.
 
     python tools/update_time.py --workload fe|ldoor [--scale 1.0] [--steps 20] [--warmup 5] [--out FILE]
+
+--shards N --split stripes|rows measures the sharded handle instead (vbc.h vbc_sharded_update_values,
+devices = [0] * N: every shard on one GPU, no communicator), with the same protocols:
+  (a) the sharded update from a device val (graph of K updates);
+  (a') row split: the update without its pack kernel -- the N shard updates on slices of an already packed
+       val -- and the pack kernel alone as the difference of the two graph times;
+  (c) destroy + create of the sharded handle with new values, not updatable (wall clock);
+  (d) create with and without VBC_CREATE_UPDATABLE_SHARDS; (e) one B'x product.
 """
 import argparse
 import json
@@ -58,6 +66,95 @@ def wall_ms(torch, fn, reps):
     return float(np.median(times)), [round(t, 1) for t in times]
 
 
+def sharded_main(args, torch, V, B):
+    import ctypes as C
+    D, L, lib = V.distributed, V._lib, V._lib.lib()
+    N, devices = args.shards, [0] * args.shards
+    esz = B.val.dtype.itemsize
+    nval = int(B.ofs[-1]) - 1
+    rng = np.random.default_rng(7)
+    v2 = rng.uniform(-1, 1, len(B.val))
+    d2 = torch.from_numpy(v2).cuda()
+
+    def with_values(v):
+        return V.SparseMatrix1DVBC(B.W, B.m, B.n, B.Phi, B.pos, B.idx, B.ofs, v)
+
+    def make(v, upd):
+        return D.MultiGPUSparseMatrix1DVBC(with_values(v), devices=devices, split=args.split, forward=False,
+                                           updatable=upd)
+    hold = {}
+    create_plain, _ = wall_ms(torch, lambda: hold.__setitem__("P", make(B.val, False)), 1)
+    create_upd, _ = wall_ms(torch, lambda: hold.__setitem__("U", make(B.val, True)), 1)
+    P, U = hold["P"], hold["U"]
+    slots = sum(U.shard_info(g)["device_bytes"] - P.shard_info(g)["device_bytes"] for g in range(N)) // 4
+    traffic = slots * (2 * esz + 4)
+
+    def recreate():
+        hold["P"].release()
+        hold["P"] = make(v2, False)
+    recreate_ms, recreate_all = wall_ms(torch, recreate, 2)
+    P = hold["P"]
+
+    s = torch.cuda.Stream()
+    x = torch.from_numpy(rng.uniform(-1, 1, B.m)).cuda()
+    y = torch.empty(B.n, dtype=torch.float64, device="cuda")
+
+    def update_dev():
+        L.check(lib.vbc_sharded_update_values(U._h, d2.data_ptr(), len(v2), L.VBC_F64, L.VBC_MEM_DEVICE, s.cuda_stream))
+    upd_us, upd_all = graph_time_us(torch, s, update_dev, args.steps, args.warmup)
+    out = {"tool": "update_time", "workload": args.workload, "scale": args.scale, "dtype": "float64", "shards": N,
+           "split": args.split, "devices": devices, "m": B.m, "n": B.n, "nval": nval, "value_slots": int(slots),
+           "update_device_us": round(upd_us, 2), "update_device_us_all": upd_all,
+           "update_traffic_bytes": int(traffic)}
+    if args.split == "rows" and N > 1:  # the shard updates alone, on slices of a val packed beforehand
+        kind = L.VBC_SPLIT_ROWS
+        vbase = np.zeros(N + 1, np.int64)
+        nruns = C.c_int64()
+        plan = lambda runs: L.check(lib.vbcx_sharded_value_plan(
+            B.m, B.n, 0, None, len(B.Phi), B.Phi.spl.ctypes.data, B.pos.ctypes.data, B.idx.ctypes.data,
+            B.ofs.ctypes.data, esz, N, kind, None, vbase.ctypes.data, None, C.byref(nruns),
+            None if runs is None else runs.ctypes.data, 0 if runs is None else len(runs)))
+        plan(None)
+        runs = np.zeros((nruns.value, 3), np.int64)
+        plan(runs)
+        src = np.repeat(runs[:, 0] - runs[:, 1], runs[:, 2]) + np.arange(nval)
+        packed = d2[torch.from_numpy(src).cuda()].contiguous()
+        hs = [U.shard_handle(g) for g in range(N)]
+
+        def shards_only():
+            for g in range(N):
+                cnt = int(vbase[g + 1] - vbase[g])
+                if cnt:
+                    L.check(lib.vbc_update_values(hs[g], packed.data_ptr() + int(vbase[g]) * esz, cnt, L.VBC_F64,
+                                                  L.VBC_MEM_DEVICE, s.cuda_stream))
+        only_us, only_all = graph_time_us(torch, s, shards_only, args.steps, args.warmup)
+        pack_us = upd_us - only_us
+        out.update({"runs": int(nruns.value), "mean_run_elements": round(nval / max(nruns.value, 1), 1),
+                    "shard_updates_only_us": round(only_us, 2), "shard_updates_only_us_all": only_all,
+                    "pack_us": round(pack_us, 2), "pack_traffic_bytes": int(2 * nval * esz + 16 * nruns.value),
+                    "pack_TBs": round((2 * nval * esz + 16 * nruns.value) / (pack_us * 1e-6) / 1e12, 3)})
+        update_dev()  # leave U holding v2 again
+    prod_us, prod_all = graph_time_us(torch, s, lambda: V.mul_(y, U.T, x), args.steps, args.warmup)
+    y2 = torch.empty_like(y)
+    V.mul_(y2, P.T, x)
+    V.mul_(y, U.T, x)
+    torch.cuda.synchronize()
+    out.update({"update_frac_of_8TBs": round(traffic / (upd_us * 1e-6) / 8e12, 3),
+                "recreate_ms": round(recreate_ms, 1), "recreate_ms_all": recreate_all,
+                "create_ms": round(create_plain, 1), "create_updatable_ms": round(create_upd, 1),
+                "product_us": round(prod_us, 2), "product_us_all": prod_all,
+                "update_below_recreate": bool(upd_us * 1e-3 < recreate_ms),
+                "bitwise_equal_to_recreated": bool(torch.equal(y, y2)),
+                "single_handle_update_us": 278, "single_handle_recreate_ms": 489,
+                "steps": args.steps, "warmup": args.warmup})
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    return 0 if out["update_below_recreate"] and out["bitwise_equal_to_recreated"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="fe", choices=["fe", "ldoor"])
@@ -65,6 +162,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--shards", type=int, default=0, help="N > 0: the sharded handle on devices = [0] * N")
+    ap.add_argument("--split", default="stripes", choices=["stripes", "rows"])
     args = ap.parse_args()
     import torch
 
@@ -72,6 +171,8 @@ def main():
     import sparsematrixvbcs_amd as V
 
     B = bench.build_matrix(args.workload, np.float64, args.scale)
+    if args.shards > 0:
+        return sharded_main(args, torch, V, B)
     esz = B.val.dtype.itemsize
     rng = np.random.default_rng(7)
     v2 = rng.uniform(-1, 1, len(B.val))
