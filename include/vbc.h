@@ -25,7 +25,10 @@
  * version at load time: 3.x changed vbc_info (VBC_INFO_SIZE bytes, written whole by vbc_get_info) and
  * added the I64 / I32 / BOOL eltypes, the sharded 2D handle and the *_ex sharded product; 3.3 added
  * VBC_CREATE_UPDATABLE and vbc_update_values; 3.4 added VBC_CREATE_UPDATABLE_SHARDS and
- * vbc_sharded_update_values (vbc_info unchanged by both). */
+ * vbc_sharded_update_values (vbc_info unchanged by both).  VBC_CREATE_NARROW_VALUES came without a version
+ * bump (vbc_version() still returns 30400, no new symbol): a binding detects the capability by a create with
+ * the flag succeeding and by vbc_info.planar_mask bits 12 / 13; a library without it refuses nothing and
+ * never sets them. */
 #define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
@@ -106,6 +109,23 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       span.  VBC_CREATE_UPDATABLE (0x20) itself stays refused by the sharded
                                       creates, as in 3.3: callers of that version and a test rely on the refusal,
                                       so the sharded capability has its own bit. */
+
+#define VBC_CREATE_NARROW_VALUES 0x80u /* vbc1d_create_ex / vbc2d_create_ex / vbc_csc_create_ex with
+                                      types->val_dtype == VBC_F32 and types->compute_dtype == VBC_F64 only: every
+                                      width bucket that create lays out slotted (either direction, any key form,
+                                      width 1..8 or the runtime width) keeps its values as Float32 in device
+                                      memory and the kernel widens them in registers when it folds them.
+                                      Widening is exact and the flag changes no layout decision (buckets, chunks,
+                                      lanes per row, ranges, key form, launch groups: those of the handle created
+                                      without it), so every product is bit-identical to that handle's.  Buckets in
+                                      any other layout (planar family, swept, merge, panel / tiles) keep Float64
+                                      values; a handle may mix both.  vbc_info.planar_mask bits 12 / 13 say whether
+                                      a B'x / forward bucket stores narrow values; bytes_t, bytes_f and
+                                      device_bytes count the bytes really stored.  Refused (VBC_INVALID_ARG, no
+                                      device work, no handle): any other (val_dtype, compute_dtype) pair, the
+                                      creates without vbc_types (their eltypes are equal), VBC_CREATE_UPDATABLE
+                                      in the same call (the update kernel writes quads of the compute eltype),
+                                      and both sharded creates. */
 
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
@@ -387,7 +407,9 @@ typedef struct vbc_info {
                                layout has tile-granular buckets (u, w <= 4 tiles: one key and one u-row X
                                block per tile, spmm_tiles); bit 10: reserved (0; round 5's staged-X tile
                                form); bit 11: the forward product of 3 x 3 fp64 node blocks in the lane-pair
-                               layout of the transposed blocks (spmv_planar_pair DOT, round 6) */
+                               layout of the transposed blocks (spmv_planar_pair DOT, round 6); bit 12: some
+                               B'x slotted bucket stores Float32 values on this Float64 handle
+                               (VBC_CREATE_NARROW_VALUES), bit 13: some forward bucket does */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

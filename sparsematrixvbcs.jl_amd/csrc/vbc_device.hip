@@ -29,6 +29,26 @@ struct MapRecorder {
 };
 static thread_local MapRecorder *g_rec = nullptr;
 
+// VBC_CREATE_NARROW_VALUES: set by the *_ex creates (which validate the flag and the eltype pair) around
+// their call of the plain create, read by create_common.  The plain creates themselves refuse the flag.
+static thread_local bool g_narrow = false;
+struct NarrowScope {
+    explicit NarrowScope(bool on) { g_narrow = on; }
+    ~NarrowScope() { g_narrow = false; }
+};
+
+// Whether every value of an fp64 array is a widened Float32 (NaNs included), so that storing it as a
+// float and widening it again gives the same bits.
+static bool all_float_exact(const char *val, int64_t n)
+{
+    const double *d = reinterpret_cast<const double *>(val);
+    for (int64_t i = 0; i < n; i++) {
+        const double back = (double)(float)d[i];
+        if (std::memcmp(&back, &d[i], 8) != 0) return false;
+    }
+    return true;
+}
+
 void set_error(const char *fmt, ...)
 {
     char buf[1024];
@@ -609,7 +629,13 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
     ps.rows = rows;
     ps.real = real;
     ps.keys.resize(E);
-    ps.o_val = ar.reserve(E * w * esz * (pair ? 3 : 1));
+    // VBC_CREATE_NARROW_VALUES: a slotted (non-planar) bin of an fp64 handle keeps its values as floats.  `val`
+    // holds them widened (exactly), so narrowing gives the caller's bits back.  Only the stored size changes:
+    // everything above was decided with esz.
+    const bool narrow = h->narrow_values && !planar && esz == 8;
+    const int vsz = narrow ? 4 : esz;
+    b.vsz = narrow ? 4 : 0;
+    ps.o_val = ar.reserve(E * w * vsz * (pair ? 3 : 1));
     ps.o_out = ar.reserve(std::max<size_t>(out.size(), 1) * 4);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
     ps.o_rchunk = ar.reserve(rchunk.size() * 4);
@@ -693,6 +719,10 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
                         if (real_row && cc < wsrc && en->voff >= 0) std::memcpy(dst, val + (en->voff + cc) * esz, (size_t)esz);
                         else std::memset(dst, 0, (size_t)esz);
                     }
+                } else if (narrow) {  // (never planar, so never a run with holes: voff >= 0)
+                    float *dst = reinterpret_cast<float *>(vv) + e * w;
+                    const double *src = reinterpret_cast<const double *>(val) + (real_row ? en->voff : 0);
+                    for (int cc = 0; cc < w; cc++) dst[cc] = (real_row && cc < wsrc) ? (float)src[cc] : 0.0f;
                 } else if (real_row) {
                     std::memcpy(vv + e * w * esz, val + en->voff * esz, (size_t)wsrc * esz);
                     if (wsrc < w) std::memset(vv + (e * w + wsrc) * esz, 0, (size_t)(w - wsrc) * esz);
@@ -1565,7 +1595,7 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
             const double f = (double)ps.real / (double)std::max<int64_t>(1, ps.rows * ps.b.rpi);
             h->bytes_t += ps.real * (int64_t)ps.b.w * h->esz + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
         } else {
-            h->bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * h->esz + ps.key_bytes;
+            h->bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
         }
     }
     L.total_ranges = range0;
@@ -1972,7 +2002,7 @@ static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena
             one.push_back(std::move(ps));
             commit_launch_keys(h, one, ar);
             const PendingSlot &p1 = one[0];
-            h->bytes_f += p1.rows * p1.b.rpi * (int64_t)w * h->esz + p1.key_bytes +
+            h->bytes_f += p1.rows * p1.b.rpi * (int64_t)w * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
                           (int64_t)sout.size() * h->esz;
             for (int32_t i : sout) any[i] = 1;
             pbs.push_back({});
@@ -2859,6 +2889,7 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
     h->dtype = dtype;
     h->esz = elem_size(dtype);
     h->device = device;
+    h->narrow_values = g_narrow && dtype == VBC_F64;
     const char *v = static_cast<const char *>(val);
     h->nnz = dtype == VBC_F64 ? count_nonzeros<double>(v, nval)
            : dtype == VBC_F32 ? count_nonzeros<float>(v, nval) : count_nonzeros<int64_t>(v, nval);
@@ -3032,7 +3063,11 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
         if (st == VBC_OK) {
             const int64_t bt = h->bytes_t;
             const size_t c0 = ar.host.size();
+            // (a stripe that stores one row twice had its copies summed in fp64: such values stay wide)
+            const bool nv = h->narrow_values;
+            h->narrow_values = nv && all_float_exact(cv.data(), (int64_t)(cv.size() / 8));
             st = build_transposed(h, c, cv.data(), ar, ptf, stf, swf, h->lft, fill_tf);
+            h->narrow_values = nv;
             if (g_rec) g_rec->canon.emplace_back(c0, ar.host.size());
             h->bytes_f = h->bytes_t - bt;
             h->bytes_t = bt;
@@ -3173,6 +3208,15 @@ static int create_updatable(vbc_handle **out, F &&create)
 
 // VBC_CREATE_UPDATABLE_SHARDS belongs to the sharded creates (vbc_sharded.cpp), which pass VBC_CREATE_UPDATABLE on
 // to their shards; the plain and *_ex creates end here.
+static int refuse_narrow_flag(vbc_handle **out, const char *why)
+{
+    if (out) *out = nullptr;
+    return fail(VBC_INVALID_ARG, why);
+}
+constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES needs Float32 values on a Float64 handle: pass it to "
+                                     "vbc1d_create_ex / vbc2d_create_ex / vbc_csc_create_ex (the creates without "
+                                     "vbc_types store the compute eltype)";
+
 static int refuse_sharded_flag(vbc_handle **out)
 {
     if (out) *out = nullptr;
@@ -3223,6 +3267,7 @@ int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, c
                  int64_t nval, int dtype, int device, unsigned flags)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
     if (!(flags & VBC_CREATE_UPDATABLE))
         return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
@@ -3300,6 +3345,7 @@ int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, i
                  int device, unsigned flags)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
     if (!(flags & VBC_CREATE_UPDATABLE))
         return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
@@ -3386,6 +3432,7 @@ int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr
                    const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
     if (!(flags & VBC_CREATE_UPDATABLE)) return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags);
     const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
     // the tags go into an nzval-shaped array, before the column blocking below copies them into its stripes
@@ -3463,6 +3510,16 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     if (h->has_ft)  // the forward product on C = Bᵀ: its split bins sum P slices too (bit 3, as a split forward)
         for (const SlotBin &b : h->lft.pbins)
             if (b.split > 1) info->planar_mask |= 8;
+    if (h->has_t)
+        for (const SlotBin &b : h->lt.sbins)
+            if (b.vsz) info->planar_mask |= 1 << 12;  // B'x slotted buckets of Float32 values (VBC_CREATE_NARROW_VALUES)
+    if (h->has_f)
+        for (const auto &l : h->lf)
+            for (const SlotBin &b : l.sbins)
+                if (b.vsz) info->planar_mask |= 1 << 13;  // forward ones
+    if (h->has_ft)
+        for (const SlotBin &b : h->lft.sbins)
+            if (b.vsz) info->planar_mask |= 1 << 13;
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3694,6 +3751,22 @@ static int convert_values(const void *val, int64_t nval, const vbc_types *t, std
     return VBC_OK;
 }
 
+// VBC_CREATE_NARROW_VALUES on an *_ex create: checked before any device work; the flag is then taken out of
+// `flags` and handed to create_common through NarrowScope.
+static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, bool &narrow)
+{
+    narrow = false;
+    if (!(flags & VBC_CREATE_NARROW_VALUES)) return VBC_OK;
+    if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
+        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES needs val_dtype VBC_F32 and compute_dtype VBC_F64");
+    if (flags & VBC_CREATE_UPDATABLE)
+        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES cannot be combined with VBC_CREATE_UPDATABLE (the update "
+                                       "kernel writes values of the compute eltype)");
+    flags &= ~VBC_CREATE_NARROW_VALUES;
+    narrow = true;
+    return VBC_OK;
+}
+
 static int check_types(const vbc_types *t)
 {
     if (!t) return fail(VBC_INVALID_ARG, "NULL vbc_types");
@@ -3730,6 +3803,8 @@ int vbc1d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L
                     unsigned flags)
 {
     if (int st = check_types(t)) return st;
+    bool narrow;
+    if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (L < 0 || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad stripe arrays");
     Idx64 S, P, I, O;
     S.set(spl, t->index_bits, L + 1);
@@ -3740,6 +3815,7 @@ int vbc1d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L
     I.set(idx, t->index_bits, q);
     std::vector<char> cv;
     if (int st = convert_values(val, nval, t, cv)) return st;
+    NarrowScope ns(narrow);
     return vbc1d_create(out, m, n, W, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval, t->compute_dtype,
                         device, flags);
 }
@@ -3749,6 +3825,8 @@ int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W
                     int64_t nval, const vbc_types *t, int device, unsigned flags)
 {
     if (int st = check_types(t)) return st;
+    bool narrow;
+    if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (K < 0 || L < 0 || !pspl || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad partition arrays");
     Idx64 PS, S, P, I, O;
     PS.set(pspl, t->index_bits, K + 1);
@@ -3760,6 +3838,7 @@ int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W
     I.set(idx, t->index_bits, q);
     std::vector<char> cv;
     if (int st = convert_values(val, nval, t, cv)) return st;
+    NarrowScope ns(narrow);
     return vbc2d_create(out, m, n, U, W, K, PS.p, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval,
                         t->compute_dtype, device, flags);
 }
@@ -3768,6 +3847,8 @@ int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr
                       const void *nzval, const vbc_types *t, int device, unsigned flags)
 {
     if (int st = check_types(t)) return st;
+    bool narrow;
+    if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (n < 0 || !colptr) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
     Idx64 CP, RV;
     CP.set(colptr, t->index_bits, n + 1);
@@ -3776,6 +3857,7 @@ int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr
     RV.set(rowval, t->index_bits, nnz);
     std::vector<char> cv;
     if (int st = convert_values(nzval, nnz, t, cv)) return st;
+    NarrowScope ns(narrow);
     return vbc_csc_create(out, m, n, CP.p, RV.p, cv.empty() ? nzval : cv.data(), t->compute_dtype, device, flags);
 }
 

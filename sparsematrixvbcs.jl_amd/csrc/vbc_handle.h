@@ -125,6 +125,7 @@ struct vbc_handle {
     size_t arena_bytes = 0;
     size_t arena_used = 0;        // bytes of the host image the arena was uploaded from
     bool updatable = false;       // VBC_CREATE_UPDATABLE: `umap` is built, vbc_update_values is allowed
+    bool narrow_values = false;   // VBC_CREATE_NARROW_VALUES (fp64 handle of Float32 values): slotted bins store floats
     vbc::ValueMap umap;
     bool has_t = false, has_f = false, has_m = false;
     vbc::PanelLaunch lm;          // multi-RHS transposed product on matrix cores (VBC_CREATE_MULTI)

@@ -135,7 +135,8 @@ struct SlotBin {
     const int16_t *lseg;   // ntiles * 64: lane's first segment inside its tile (== stripes of the tile: none)
     int32_t dot;           // pair layout of a forward product (vbc_planar.h run_pair DOT): per block, each output
                            // row's dot product with the x slice is added to its sum (the reference's forward order)
-    int32_t pad_dot;
+    int32_t vsz;           // slotted: 4 = `val` holds Float32 values on an fp64 handle (VBC_CREATE_NARROW_VALUES:
+                           // widened in registers, every bin of the launch alike); 0 = values of the compute eltype
 };
 
 // Runs with holes (SlotBin::holes): the run's stored-row mask above the gather index of its first key.
@@ -210,7 +211,8 @@ int launch_sweep(int esz, int kind, const SweepBin *d_bins, int nbins, int total
 
 constexpr int kWonlyNarrow2 = 102;  // spmv_slots WONLY: fp32 B'x w = 2 folded two segments per lane (run_slots_narrow)
 // Launches spmv_slots (vbc_slots.hip): returns the hipError_t of the launch.
-int launch_slots(int esz, int kind, const SlotBin *d_bins, int nbins, int total_ranges, bool faste, int xcd, int u, int diag, int stage, bool kc,
+// vsz: size of the stored values (esz, or 4 on an fp64 launch whose bins all keep Float32 values).
+int launch_slots(int esz, int vsz, int kind, const SlotBin *d_bins, int nbins, int total_ranges, bool faste, int xcd, int u, int diag, int stage, bool kc,
                  int wonly, const void *x, void *y, double alpha, double beta, bool rd, hipStream_t stream);
 int occupancy_slots(int esz, int kind);
 // vbc_planar.hip

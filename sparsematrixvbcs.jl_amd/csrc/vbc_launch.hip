@@ -61,7 +61,11 @@ static int launch_group(const Launch &L, int kind, const void *x, void *y, doubl
         if (wonly == 2 && narrow) wonly = kWonlyNarrow2;
         else if (wonly == 2 && kind == 0 && sizeof(T) == 4) wonly = -1;  // mixed narrow / plain w = 2 bins
         if (L.sbins[0].nowonly) wonly = -1;  // VBC_SLOT_WONLY=0 (A/B knob)
-        const hipError_t e = (hipError_t)launch_slots((int)sizeof(T), kind, L.d_sbins, (int)L.sbins.size(), L.slot_ranges,
+        // VBC_CREATE_NARROW_VALUES: every slotted bin of the launch stores Float32 values, or none does
+        const int vsz = L.sbins[0].vsz > 0 ? L.sbins[0].vsz : (int)sizeof(T);
+        for (const SlotBin &sb : L.sbins)
+            if (sb.vsz != L.sbins[0].vsz) return fail(VBC_INVALID_ARG, "internal: slotted bins of one launch store different value types");
+        const hipError_t e = (hipError_t)launch_slots((int)sizeof(T), vsz, kind, L.d_sbins, (int)L.sbins.size(), L.slot_ranges,
                                                       faste, xcd, L.sbins[0].u, L.sbins[0].diag, stage, L.sbins[0].kc != 0,
                                                       wonly, x, y, alpha, beta, rd, stream);
         if (e != hipSuccess) {

@@ -42,7 +42,11 @@ __device__ __forceinline__ T slot_reduce(const T (&v)[V], int lane, int sub, int
 // fewer write events interleaved with the load stream.
 // KC: compressed keys -- a scalar per-row base (LAST in bit 30) plus an int16 delta per slot
 // (INT16_MIN marks padding): 2 index bytes per entry instead of 4.
-template <typename T, int KIND, int W_, int U, bool FASTE, int DIAG = 0, int NB = 0, bool KC = false>
+// S: the stored value type (default T).  S = float with T = double (VBC_CREATE_NARROW_VALUES): the stream
+// loads and the pipeline registers hold floats -- the same V elements per lane, contiguous across the
+// wave at half the bytes -- and each value is widened (exactly) as the operand of its fmadd.  V and LPR
+// stay those of T, so slots, lanes and the summation order are the wide kernel's.
+template <typename T, int KIND, int W_, int U, bool FASTE, int DIAG = 0, int NB = 0, bool KC = false, typename S = T>
 __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, const T *__restrict__ x,
                                           T *__restrict__ y, T alpha, T beta, bool rd, char *lds_wave, int *lds_out)
 {
@@ -57,7 +61,7 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
     if (R0 >= R1) return;
     int c = G(b.rchunk)[r];
     const int lslot = active ? slot : 0, lsub = active ? sub : 0;
-    const gptr<const T> val = G(static_cast<const T *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const T> xg = G(x);
     constexpr int XV = KIND == 0 ? 1 : V;
@@ -67,7 +71,7 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
     typedef __attribute__((address_space(4))) const uint32_t *cptr;  // scalar (constant) loads
     const cptr bases = (cptr)b.base;
     const cptr doffs = (cptr)b.kdoff;
-    auto load = [&](int R, uint32_t (&kk)[U], uint32_t (&bs)[U], T (&v)[U][V]) {
+    auto load = [&](int R, uint32_t (&kk)[U], uint32_t (&bs)[U], S (&v)[U][V]) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int Rc = min(R + u, R1 - 1);
@@ -79,7 +83,7 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
                 kk[u] = __builtin_nontemporal_load(key + p);
                 bs[u] = 0;
             }
-            ld_stream<T, V>(val + p * w + lsub * V, v[u]);
+            ld_stream<S, V>(val + p * w + lsub * V, v[u]);
         }
     };
     constexpr uint32_t kPad16 = 0xFFFF8000u;  // INT16_MIN sign-extended
@@ -198,7 +202,7 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
     // scalar branch around the fold.
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
-    auto compute = [&](int R, const uint32_t (&kk)[U], const uint32_t (&bs)[U], const T (&v)[U][V],
+    auto compute = [&](int R, const uint32_t (&kk)[U], const uint32_t (&bs)[U], const S (&v)[U][V],
                        const T (&xv)[U][XV]) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -207,7 +211,7 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
 #pragma unroll
             for (int e = 0; e < V; e++) {
                 const T xe = pad ? T(0) : xv[u][KIND == 0 ? 0 : e];
-                const T nv = fmadd(v[u][e], xe, acc[e]);
+                const T nv = fmadd((T)v[u][e], xe, acc[e]);
                 acc[e] = live ? nv : acc[e];
             }
             const uint32_t lastw = KC ? bs[u] : (uint32_t)__builtin_amdgcn_readfirstlane((int)kk[u]);
@@ -219,7 +223,8 @@ __device__ __forceinline__ void run_slots(const SlotBin &b, int r, int lane, con
     // Every path to the loop header has consumed every load it issued, so the header's wait for the
     // keys of the next step is counted (vmcnt(n)), never a drain.
     uint32_t kA[U], kB[U], bA[U], bB[U];
-    T vA[U][V], vB[U][V], xv[U][XV];
+    S vA[U][V], vB[U][V];
+    T xv[U][XV];
     load(R0, kA, bA, vA);
     __builtin_amdgcn_s_waitcnt(0);  // prologue drained: the loop header merges the back-edge state only
     for (int R = R0; R < R1; R += 2 * U) {
@@ -415,7 +420,9 @@ __host__ __device__ constexpr int slot_step(int w, int U)
 // WONLY >= 0: every bin of the launch has width WONLY, so only that case is compiled -- the register
 // budget is that width's (the all-width switch spilled 83 / ~600 SGPRs in fp64 / fp32, the maximum over
 // cases it never runs on FE).
-template <typename T, int KIND, int U, bool FASTE, int DIAG = 0, int NB = 0, bool KC = false, int WONLY = -1>
+// S: stored value type of every bin of the launch (run_slots).
+template <typename T, int KIND, int U, bool FASTE, int DIAG = 0, int NB = 0, bool KC = false, int WONLY = -1,
+          typename S = T>
 __global__ __launch_bounds__(kBlockThreads) void spmv_slots(const SlotBin *__restrict__ bins, int nbins,
                                                             int total_ranges, int xcd_chunk, const T *__restrict__ x,
                                                             T *__restrict__ y, T alpha, T beta, int rd_i)
@@ -451,20 +458,20 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_slots(const SlotBin *__res
         }
     }
     if constexpr (WONLY >= 0 && WONLY != kWonlyNarrow2) {
-        run_slots<T, KIND, WONLY, slot_step<T>(WONLY, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds,
-                                                                              lds_out);
+        run_slots<T, KIND, WONLY, slot_step<T>(WONLY, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd,
+                                                                                 lds, lds_out);
         return;
     }
     switch (b.wkey) {
-    case 0: run_slots<T, KIND, 0, slot_step<T>(0, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 1: run_slots<T, KIND, 1, slot_step<T>(1, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 2: run_slots<T, KIND, 2, slot_step<T>(2, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 3: run_slots<T, KIND, 3, slot_step<T>(3, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 4: run_slots<T, KIND, 4, slot_step<T>(4, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 5: run_slots<T, KIND, 5, slot_step<T>(5, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 6: run_slots<T, KIND, 6, slot_step<T>(6, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 7: run_slots<T, KIND, 7, slot_step<T>(7, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
-    case 8: run_slots<T, KIND, 8, slot_step<T>(8, U), FASTE, DIAG, NB, KC>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 0: run_slots<T, KIND, 0, slot_step<T>(0, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 1: run_slots<T, KIND, 1, slot_step<T>(1, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 2: run_slots<T, KIND, 2, slot_step<T>(2, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 3: run_slots<T, KIND, 3, slot_step<T>(3, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 4: run_slots<T, KIND, 4, slot_step<T>(4, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 5: run_slots<T, KIND, 5, slot_step<T>(5, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 6: run_slots<T, KIND, 6, slot_step<T>(6, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 7: run_slots<T, KIND, 7, slot_step<T>(7, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
+    case 8: run_slots<T, KIND, 8, slot_step<T>(8, U), FASTE, DIAG, NB, KC, S>(b, r, lane, x, y, alpha, beta, rd, lds, lds_out); break;
     default: break;
     }
 }

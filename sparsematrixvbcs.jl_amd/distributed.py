@@ -209,7 +209,10 @@ class ShardedSparseMatrix1DVBC:
     per rank.  See the module docstring for the two splits and which product needs a collective."""
 
     def __init__(self, B, rank, world, group=None, local_mul=None, device=None, split="stripes", comm="device",
-                 directions="tf", updatable=False):
+                 directions="tf", updatable=False, narrow=False):
+        from . import _lib as _L
+        if narrow or getattr(B, "narrow", False):  # (vbc.h VBC_CREATE_NARROW_VALUES: single-GPU handles only)
+            raise _L.ArgumentError("narrow value storage is not supported on multi-GPU matrices")
         if split == "auto":  # by the cost model: predicted kernel + collective time of the products to run
             split = choose_split(B, world, directions)
         if split not in ("stripes", "rows"):
@@ -405,9 +408,11 @@ class MultiGPUSparseMatrix1DVBC:
     the handle's compute eltype, multiply_1DVBC.jl:9,85,102): vbc_sharded_mul_ex carries them."""
 
     def __init__(self, B, devices=(0,), split="stripes", transposed=True, forward=True, serial=False,
-                 updatable=False):
+                 updatable=False, narrow=False):
         import ctypes as C
         from . import _lib as _L
+        if narrow or getattr(B, "narrow", False):  # (vbc.h VBC_CREATE_NARROW_VALUES: the sharded creates refuse it)
+            raise _L.ArgumentError("narrow value storage is not supported on multi-GPU matrices")
         if split not in ("stripes", "rows", "auto"):
             raise ValueError("split must be 'stripes', 'rows' or 'auto'")
         self.m, self.n, self.W = B.m, B.n, B.W

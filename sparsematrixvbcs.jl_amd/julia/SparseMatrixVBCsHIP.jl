@@ -84,7 +84,10 @@ end
 
 Device-resident copies of `B`, one libvbc handle per compute eltype met (created on first use by
 `mul!`), freed by a finalizer (`vbc_destroy`).  The layout is immutable; with `updatable=true`
-(VBC_CREATE_UPDATABLE) `update_values!(M, val)` overwrites the stored values in place.
+(VBC_CREATE_UPDATABLE) `update_values!(M, val)` overwrites the stored values in place.  With `narrow=true`
+(VBC_CREATE_NARROW_VALUES) a Float32 matrix applied to Float64 vectors keeps its values as Float32 on the
+device (slotted buckets; same bits as without); for any other eltype pair the keyword is ignored.  `narrow`
+and `updatable` together throw an ArgumentError.
 """
 mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
     host::SparseMatrix1DVBC{W, Tv, Ti}
@@ -94,10 +97,12 @@ mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
 end
 
 function HIPSparseMatrix1DVBC(B::SparseMatrix1DVBC{W, Tv, Ti}; device::Integer=0, forward::Bool=true,
-                              transposed::Bool=true, multi::Bool=false, updatable::Bool=false) where {W, Tv, Ti}
+                              transposed::Bool=true, multi::Bool=false, updatable::Bool=false,
+                              narrow::Bool=false) where {W, Tv, Ti}
+    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
             (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
-            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0))
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0))
     M = HIPSparseMatrix1DVBC{W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -121,10 +126,12 @@ mutable struct HIPSparseMatrixVBC{U, W, Tv, Ti}
 end
 
 function HIPSparseMatrixVBC(B::SparseMatrixVBC{U, W, Tv, Ti}; device::Integer=0, forward::Bool=true,
-                            transposed::Bool=true, multi::Bool=false, updatable::Bool=false) where {U, W, Tv, Ti}
+                            transposed::Bool=true, multi::Bool=false, updatable::Bool=false,
+                            narrow::Bool=false) where {U, W, Tv, Ti}
+    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
             (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
-            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0))
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0))
     M = HIPSparseMatrixVBC{U, W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -149,8 +156,11 @@ mutable struct HIPSparseMatrixCSC{Tv, Ti}
     handles::Dict{Cint, Ptr{Cvoid}}
 end
 
-function HIPSparseMatrixCSC(A::SparseMatrixCSC{Tv, Ti}; device::Integer=0, updatable::Bool=false) where {Tv, Ti}
-    M = HIPSparseMatrixCSC{Tv, Ti}(A, device, VBC_CREATE_TRANSPOSED | (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)),
+function HIPSparseMatrixCSC(A::SparseMatrixCSC{Tv, Ti}; device::Integer=0, updatable::Bool=false,
+                            narrow::Bool=false) where {Tv, Ti}
+    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
+    M = HIPSparseMatrixCSC{Tv, Ti}(A, device, VBC_CREATE_TRANSPOSED | (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) |
+                                   (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0)),
                                    Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -174,7 +184,9 @@ Base.eltype(A::HIPMatrix) = eltype(A.host)
 function handle_for(A::HIPMatrix, ::Type{Ty}) where {Ty}
     cdt = compute_dtype(Ty)
     cdt == VBC_I64 && eltype(A) <: AbstractFloat && throw(InexactError(:convert, Ty, zero(eltype(A))))
-    get!(() -> _create(A.host, A.device, A.flags, cdt), A.handles, cdt)
+    # narrow values: only Float32 values on a Float64 handle (the library refuses the flag for any other pair)
+    flags = (eltype(A) === Float32 && cdt == VBC_F64) ? A.flags : A.flags & ~VBC_CREATE_NARROW_VALUES
+    get!(() -> _create(A.host, A.device, flags, cdt), A.handles, cdt)
 end
 
 _host_values(A::HIPSparseMatrixCSC) = A.host.nzval
@@ -266,6 +278,7 @@ const HIPShardedSparseMatrix1DVBC = HIPShardedSparseMatrix  # round-2 name
 
 const VBC_CREATE_SERIAL = Cuint(8)
 const VBC_CREATE_UPDATABLE = Cuint(0x20)
+const VBC_CREATE_NARROW_VALUES = Cuint(0x80)  # Float32 values kept narrow on a Float64 handle (slotted buckets)
 const VBC_CREATE_UPDATABLE_SHARDS = Cuint(0x40)  # the sharded creates only (they refuse 0x20)
 
 _split_code(split) = split === :stripes ? VBC_SPLIT_STRIPES : split === :rows ? VBC_SPLIT_ROWS : VBC_SPLIT_AUTO

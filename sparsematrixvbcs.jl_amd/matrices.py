@@ -75,7 +75,10 @@ class _DeviceMatrix:
         `compute` = the vbc_dtype the product runs in (eltype(y)); default: the value eltype's own
         (floats) or exact Int64 (integers, Bool).  One handle per (device, layout, compute).
         Setting `B.serial = True` before the first product builds layouts that keep the reference's
-        serial per-stripe summation order whatever the size (vbc.h VBC_CREATE_SERIAL)."""
+        serial per-stripe summation order whatever the size (vbc.h VBC_CREATE_SERIAL).
+        Setting `B.narrow = True` before the first product keeps a float32 matrix's values as Float32 on
+        the device when the product computes in Float64 (vbc.h VBC_CREATE_NARROW_VALUES: slotted buckets
+        only, products bit-identical); for any other eltype pair the attribute is ignored."""
         if multi:  # matrix-core panels: of B for B'X, of Bᵀ for B·X
             flags = _L.VBC_CREATE_MULTI if trans else _L.VBC_CREATE_MULTI_FORWARD
         else:
@@ -89,6 +92,12 @@ class _DeviceMatrix:
             flags |= _L.VBC_CREATE_SERIAL  # the reference's serial per-stripe order in every layout
         if getattr(self, "updatable", False):
             flags |= _L.VBC_CREATE_UPDATABLE  # update_values rewrites the stored values in place
+        if getattr(self, "narrow", False):
+            if getattr(self, "updatable", False):
+                raise _L.ArgumentError("B.narrow and B.updatable cannot be combined (the update kernel writes "
+                                       "values of the compute eltype)")
+            if not multi and self._val.dtype == np.float32 and compute == _L.VBC_F64:
+                flags |= _L.VBC_CREATE_NARROW_VALUES  # Float32 values in HBM, widened in registers
         return self._handles.get((int(device), flags, compute),
                                  lambda out: self._create(out, int(device), flags, compute))
 
@@ -98,7 +107,11 @@ class _DeviceMatrix:
     def info(self, device=0, trans=True, multi=False, compute=None):
         inf = _L.vbc_info()
         _L.check(_L.lib().vbc_get_info(self.handle(device, trans, multi, compute), C.byref(inf)), "info")
-        return {f: getattr(inf, f) for f, _ in _L.vbc_info._fields_}
+        d = {f: getattr(inf, f) for f, _ in _L.vbc_info._fields_}
+        # derived keys (planar_mask bits 12 / 13): a B'x / forward slotted bucket stores Float32 values
+        d["narrow_t"] = bool(inf.planar_mask & (1 << 12))
+        d["narrow_f"] = bool(inf.planar_mask & (1 << 13))
+        return d
 
     def release(self):
         self._handles.release()
