@@ -23,6 +23,7 @@
 #define VBC_API __attribute__((visibility("default")))  /* the library builds with -fvisibility=hidden */
 #endif
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -109,6 +110,37 @@ VBC_API int vbcx_sharded_value_plan(int64_t m, int64_t n, int64_t K, const int64
                                     const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
                                     int compute_size, int ngpus, int split, int64_t *cuts, int64_t *vbase,
                                     int64_t *run_begin, int64_t *nruns, int64_t *runs, int64_t run_capacity);
+
+/* ---- the layout planner on the host (for tests and tools; a product caller needs neither) ----
+ * A create asks the device a handful of facts, then plans the whole layout on the host (the arena image it
+ * uploads).  These two entries separate the steps, so that a layout can be checked on a machine without a GPU
+ * under the facts recorded on one.
+ *
+ * vbcx_facts: compute units and the occupancy (resident workgroups per CU, as the runtime reports them) of every
+ * kernel family, first index 0 = Float64, 1 = Float32. */
+typedef struct vbcx_facts {
+    int32_t cus;
+    int32_t occ_ranges[2][2][2][2];  /* merge kernel: [eltype][tile K = 8][pipeline depth = 3][B'x, Bx] */
+    int32_t occ_slots[2][2];         /* slotted kernels: [eltype][B'x, Bx] */
+    int32_t occ_planar[2];
+    int32_t occ_lanes[2];
+    int32_t occ_split_multi[2][3];   /* fused split launch: [eltype][P = 2, 4, 8] */
+    int32_t occ_panel[2];            /* the two multi-RHS kernels: asked only by VBC_CREATE_MULTI(_FORWARD) creates */
+    int32_t occ_tiles[2];
+} vbcx_facts;
+
+/* The facts of `device`, every row filled (needs the device). */
+VBC_API int vbcx_device_facts(int device, vbcx_facts *out);
+
+/* The arena image a create with these arguments would upload under `facts` (needs no device): the fields of
+ * vbc1d_create (pspl = NULL; U, K ignored) or vbc2d_create, checked as those do; dtype = the compute eltype of
+ * val; flags = vbc_create_flags without VBC_CREATE_UPDATABLE(_SHARDS) (VBC_CREATE_NARROW_VALUES: val holds Float32 values widened to Float64).  The
+ * environment knobs of INTEGRATION.md apply as in a create.  *bytes receives the image size; image = NULL
+ * returns only that, else capacity must hold it. */
+VBC_API int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
+                            const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
+                            const void *val, int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts,
+                            void *image, size_t capacity, size_t *bytes);
 
 #ifdef __cplusplus
 }

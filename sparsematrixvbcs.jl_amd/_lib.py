@@ -36,7 +36,7 @@ ABI_SYMBOLS = (
     "vbc_sharded_count", "vbc_sharded_shard", "vbc_sharded_split", "vbc_sharded_xspan", "vbc_sharded_update_values",
     "vbcx_partition_equi", "vbcx_partition_strict", "vbcx_partition_overlap",
     "vbcx_partition_dynamic", "vbcx_partition_dynamic_table", "vbcx_partition_block", "vbcx_1dvbc_count", "vbcx_1dvbc_fill", "vbcx_vbc_count",
-    "vbcx_vbc_fill", "vbcx_transpose_pattern", "vbcx_sharded_value_plan",
+    "vbcx_vbc_fill", "vbcx_transpose_pattern", "vbcx_sharded_value_plan", "vbcx_device_facts", "vbcx_plan_image",
 )
 
 
@@ -73,6 +73,13 @@ class vbc_info(C.Structure):
                 ("planar_run", C.c_int32), ("planar_split", C.c_int32),
                 ("planar_pair", C.c_int32), ("fwd_run", C.c_int32),
                 ("planar_mask", C.c_int32)]
+
+
+class vbcx_facts(C.Structure):
+    """include/vbc_host.h vbcx_facts: what a create asks the device (first index 0 = Float64, 1 = Float32)."""
+    _fields_ = [("cus", C.c_int32), ("occ_ranges", C.c_int32 * 2 * 2 * 2 * 2), ("occ_slots", C.c_int32 * 2 * 2),
+                ("occ_planar", C.c_int32 * 2), ("occ_lanes", C.c_int32 * 2), ("occ_split_multi", C.c_int32 * 3 * 2),
+                ("occ_panel", C.c_int32 * 2), ("occ_tiles", C.c_int32 * 2)]
 
 
 _lib = None
@@ -139,6 +146,9 @@ def lib():
         L.vbcx_vbc_fill.argtypes = [I64, I64, I64, I64, P, P, P, INT, I64, P, I64, P, P, P, P, P, I64]
         L.vbcx_transpose_pattern.argtypes = [I64, I64, P, P, P, P]
         L.vbcx_sharded_value_plan.argtypes = [I64, I64, I64, P, I64, P, P, P, P, INT, INT, INT, P, P, P, P, P, I64]
+        L.vbcx_device_facts.argtypes = [INT, C.POINTER(vbcx_facts)]
+        L.vbcx_plan_image.argtypes = [I64, I64, I64, I64, I64, P, I64, P, P, P, P, P, I64, INT, U, C.POINTER(vbcx_facts),
+                                      P, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 

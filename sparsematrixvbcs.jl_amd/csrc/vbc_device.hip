@@ -1,5 +1,7 @@
-// libvbc device side: handle creation (reference layout -> tiled HBM entry streams), product launches
-// and the C ABI of include/vbc.h.
+// libvbc handle creation and the C ABI of include/vbc.h.  A create is three steps: the device's facts
+// (gather_facts), the layout planned on the host alone (plan_layout: the builders below fill an arena image and
+// launch descriptors without device pointers from a LayoutConfig -- no HIP call, no environment), and the
+// device part (instantiate: upload, device pointers, fork streams and events).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,21 +22,32 @@ namespace vbc {
 
 static thread_local std::string g_err;
 
-// A recording build of VBC_CREATE_UPDATABLE (create_updatable below): create_common lays the arena out on the
-// host as usual, hands the image over instead of uploading it and returns no handle.  `canon`: the byte
-// ranges of the arena filled from transpose_stripes' values (the value map marks their slots, vbc_handle.h).
-struct MapRecorder {
-    std::vector<char> arena;
+// The recorder of VBC_CREATE_UPDATABLE's recording plans (create_handle below): the byte ranges of the arena
+// filled from transpose_stripes' values (the value map marks their slots, vbc_handle.h).  With a recorder
+// transpose_stripes copies the (tag) values instead of summing them.
+struct Recorder {
     std::vector<std::pair<size_t, size_t>> canon;
 };
-static thread_local MapRecorder *g_rec = nullptr;
 
-// VBC_CREATE_NARROW_VALUES: set by the *_ex creates (which validate the flag and the eltype pair) around
-// their call of the plain create, read by create_common.  The plain creates themselves refuse the flag.
-static thread_local bool g_narrow = false;
-struct NarrowScope {
-    explicit NarrowScope(bool on) { g_narrow = on; }
-    ~NarrowScope() { g_narrow = false; }
+// What the builders write besides the arena: which layouts exist and their statistics.
+struct PlanStats {
+    bool has_t = false, has_f = false, has_ft = false, has_m = false, has_mf = false;
+    bool f_scale = false;          // forward with several buckets: scale y by beta first
+    int64_t bytes_t = 0, bytes_f = 0, bytes_m = 0, bytes_mf = 0;  // matrix bytes one product streams
+    int32_t mf_group = 0;          // forward panel: widest output row group
+    int64_t panel_val_bytes = 0;   // largest bin val array of the panel layout
+    // scratch of build_transposed, rebuilt by each call:
+    int small_split = 0;           // > 1: this B'x layout is the fused small-matrix split with P waves per chunk
+    uint32_t fuse_w = 0;           // bit w: the width-w bucket belongs to the fused split (all, or the side buckets)
+};
+
+// What the builders see (as `h`): the configuration, the statistics they fill, the recorder (NULL outside a
+// recording plan).  No handle, no device.
+struct PlanCtx : LayoutConfig {
+    PlanCtx(const LayoutConfig &c, PlanStats &stats, Recorder *r, int64_t nv) : LayoutConfig(c), st(stats), rec(r), nval(nv) {}
+    PlanStats &st;
+    Recorder *rec;
+    int64_t nval;  // elements of the input val
 };
 
 // Whether every value of an fp64 array is a widened Float32 (NaNs included), so that storing it as a
@@ -109,7 +122,7 @@ struct Entry {
 };
 
 // Lay out one bucket's entry stream (segment-ordered) as tiles, ranges and fix-up slots.
-static int build_bucket(vbc_handle *h, int kind, int w, const std::vector<Entry> &ents,
+static int build_bucket(PlanCtx *h, int kind, int w, const std::vector<Entry> &ents,
                         const std::vector<int32_t> &out, int64_t total_entries, const char *val,
                         Arena &ar, int &range0, PendingBin &pb, int wsrc = 0)
 {
@@ -148,7 +161,7 @@ static int build_bucket(vbc_handle *h, int kind, int w, const std::vector<Entry>
     pb.b.out_stride = out.size() > 1 ? out[1] - out[0] : 0;
     for (size_t q = 1; q < out.size() && pb.b.out_affine; q++)
         pb.b.out_affine = (int64_t)out[q] == (int64_t)out[0] + (int64_t)q * pb.b.out_stride;
-    if (ablation_knob("VBC_NO_AFFINE")) pb.b.out_affine = 0;  // (the VBC_ABLATION build only)
+    if (h->no_affine) pb.b.out_affine = 0;  // (the VBC_ABLATION build only)
     range0 += (int)nr;
     const int64_t Rp = ntiles * tile_rows;
     pb.o_key = ar.reserve(Rp * 4);
@@ -264,7 +277,7 @@ static void commit_slot_keys(PendingSlot &ps, bool kc, Arena &ar, bool dedup)
 
 // Segments per lane of a B'x bucket whose rows are narrower than a 16-B lane vector: fp32 w = 2 folds
 // two segments side by side (run_slots_narrow); w = 1 (CSC) keeps one segment per lane (faster).
-static int slot_spl(const vbc_handle *h, int kind, int w)
+static int slot_spl(const PlanCtx *h, int kind, int w)
 {
     if (kind != 0 || !h->slot_narrow) return 1;
     return (h->esz == 4 && w == 2) ? 2 : 1;  // the only narrow form that measured faster (vbc_slots.h)
@@ -273,15 +286,15 @@ static int slot_spl(const vbc_handle *h, int kind, int w)
 // Planar chunk rows (vbc_planar.h) for a B'x bucket of width w: one stripe per lane whenever a row
 // is wider than one 16-B lane vector would hold with a single lane (fp64 w >= 3, fp32 w >= 5) and for
 // fp32 w = 3 (12-B rows, no padding to 4).
-static bool slot_planar(const vbc_handle *h, int kind, int w)
+static bool slot_planar(const PlanCtx *h, int kind, int w)
 {
-    if (kind == 0 && h->small_split > 1 && w >= 1 && w <= 8 && ((h->fuse_w >> w) & 1)) return true;  // fused split (below)
+    if (kind == 0 && h->st.small_split > 1 && w >= 1 && w <= 8 && ((h->st.fuse_w >> w) & 1)) return true;  // fused split (below)
     if (kind != 0 || h->slot_planar == 0 || w < 3 || w > 8) return false;
     return h->esz == 8 || w != 4;
 }
 
 // Slots per chunk of a bucket stored w wide (lane-vector width as in the kernel).
-static int slot_rpi(const vbc_handle *h, int kind, int w)
+static int slot_rpi(const PlanCtx *h, int kind, int w)
 {
     if (slot_planar(h, kind, w)) return 64;
     const int spl = slot_spl(h, kind, w);
@@ -352,11 +365,11 @@ constexpr double kMaskPad = 3.0;
 // costs its longest stripe's rows / P whatever its padding, and the padding rows read cached zeros.
 constexpr double kSmallPad = 4.0;
 
-static int want_slots(const vbc_handle *h, int kind, int w, const std::vector<int64_t> &sbeg,
+static int want_slots(const PlanCtx *h, int kind, int w, const std::vector<int64_t> &sbeg,
                       int64_t total_entries, int64_t gather_limit, std::vector<int64_t> &order,
                       bool *mask = nullptr, int wsrc = -1)
 {
-    const bool fused = kind == 0 && h->small_split > 1 && wsrc >= 1 && wsrc <= 8 && ((h->fuse_w >> wsrc) & 1);
+    const bool fused = kind == 0 && h->st.small_split > 1 && wsrc >= 1 && wsrc <= 8 && ((h->st.fuse_w >> wsrc) & 1);
     if (mask) *mask = false;
     const int64_t nseg = (int64_t)sbeg.size() - 1;
     const int64_t real = nseg > 0 ? sbeg[nseg] - sbeg[0] : 0;
@@ -425,7 +438,7 @@ static int want_slots(const vbc_handle *h, int kind, int w, const std::vector<in
 // come in aligned runs of R consecutive x rows -- the dof rows of a node in a stiffness operator
 // stored by node stripes (fe3d, the ldoor / ct20stif stand-ins).  The kernel then reads one key per
 // run and gathers the run's R x values at once.  VBC_SLOT_RUNS=0 disables it (A/B, tests).
-static int slot_runs(const vbc_handle *h, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg)
+static int slot_runs(const PlanCtx *h, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg)
 {
     if (h->slot_runs == 0) return 1;
     const int64_t nseg = (int64_t)sbeg.size() - 1;
@@ -447,7 +460,7 @@ static int slot_runs(const vbc_handle *h, const std::vector<Entry> &ents, const 
 // chunks balanced by rows.  ents[sbeg[q] ...] are segment q's entries (keys = gather index only).
 // pair_only: build nothing and return kBuildDeclined unless the bucket takes the lane-pair layout.
 constexpr int kBuildDeclined = -1;
-static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vector<Entry> &ents,
+static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<Entry> &ents,
                        const std::vector<int64_t> &sbeg0, const std::vector<int32_t> &out0, int64_t total_entries,
                        const char *val, Arena &ar, int &range0, PendingSlot &ps,
                        const std::vector<int64_t> &order = {}, bool mask = false, int ks = 1, bool pair_only = false)
@@ -501,8 +514,8 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
         for (int32_t c : cr) rows += c;
         // planar buckets with fewer chunks than wave slots: one chunk per workgroup of `split` waves
         split = 1;
-        if (planar && kind == 0 && h->small_split > 1 && wsrc <= 8 && ((h->fuse_w >> wsrc) & 1)) {
-            split = h->small_split;  // fused small-matrix split: one P for every bucket of the launch
+        if (planar && kind == 0 && h->st.small_split > 1 && wsrc <= 8 && ((h->st.fuse_w >> wsrc) & 1)) {
+            split = h->st.small_split;  // fused small-matrix split: one P for every bucket of the launch
         } else if (planar && h->planar_split != 0) {
             if (h->planar_split > 1) split = h->planar_split;
             else if ((double)nch / (pair ? 2 : 1) * 2 <= share) {  // in 64-stripe chunks
@@ -568,7 +581,7 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
     }
     rrow.push_back((int32_t)rows);
     nr = (int64_t)rchunk.size();
-    if (layout_knob("VBC_VERBOSE"))
+    if (h->verbose)
         fprintf(stderr, "[vbc] slot bin kind %d w %d planar %d pair %d run %d split %d chunks %lld rows %lld ranges %lld "
                 "(target share %.0f)\n", kind, w, (int)planar, (int)pair, run, split, (long long)nch, (long long)rows,
                 (long long)nr, share);
@@ -583,7 +596,7 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
     b.nranges = (int32_t)nr;
     b.nseg = (int32_t)nstripes;
     b.ks = ks;
-    b.fused = (planar && kind == 0 && split > 1 && h->small_split > 1 && wsrc <= 8 && ((h->fuse_w >> wsrc) & 1)) ? 1 : 0;
+    b.fused = (planar && kind == 0 && split > 1 && h->st.small_split > 1 && wsrc <= 8 && ((h->st.fuse_w >> wsrc) & 1)) ? 1 : 0;
     b.u = h->slot_u;
     b.diag = h->diag;
     b.xcd = (planar && split == 1) ? h->xcd_p : 0;  // split grids are small (one chunk per workgroup)
@@ -616,7 +629,7 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
     b.out_stride = out.size() > 1 ? out[1] - out[0] : 0;
     for (size_t q = 1; q < out.size() && b.out_affine; q++)
         b.out_affine = (int64_t)out[q] == (int64_t)out[0] + (int64_t)q * b.out_stride;
-    if (ablation_knob("VBC_NO_AFFINE")) b.out_affine = 0;  // (the VBC_ABLATION build only)
+    if (h->no_affine) b.out_affine = 0;  // (the VBC_ABLATION build only)
     {
         const int V = w <= 8 ? vec_elems(esz, w) : 1;
         const bool full = b.spl > 1 || planar || (RPI * (w / V) == 64 && V * esz <= 16);
@@ -738,9 +751,6 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
     // costs a dependent scalar load (its row's pattern offset) before the key itself
     const bool split_kc = split == 1 || h->split_kc;
     ps.kc_ok = kc_wanted && split_kc && slot_keys_compressible(ps.keys, rows, RPI);
-    h->slot_rows_padded += E;
-    h->slot_rows_real += real;
-    h->slot_rows_padded_last = E;
     return VBC_OK;
 }
 
@@ -756,7 +766,7 @@ static int build_slots(vbc_handle *h, int kind, int w, int wsrc, const std::vect
 // representable), 0 never; auto: a bucket the masked order would take (natural order pads beyond
 // slots_pad) with natural contiguous outputs, few empty stripes, and >= 256 stripes per resident wave
 // (sub-blocks of ~4 stripes per lane balance the streams).
-static bool want_lanes(const vbc_handle *h, int wps, int w, const std::vector<int64_t> &sbeg,
+static bool want_lanes(const PlanCtx *h, int wps, int w, const std::vector<int64_t> &sbeg,
                        const std::vector<int32_t> &out, int64_t total_entries, bool mask)
 {
     if (h->planar_lanes == 0 || !slot_planar(h, 0, w) || wps != w) return false;
@@ -773,7 +783,7 @@ static bool want_lanes(const vbc_handle *h, int wps, int w, const std::vector<in
     return (double)nseg >= 256.0 * std::max(1.0, share);
 }
 
-static int build_lanes(vbc_handle *h, int w, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
+static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
                        const std::vector<int32_t> &out, int run, int64_t total_entries, const char *val, Arena &ar,
                        PendingSlot &ps)
 {
@@ -852,7 +862,7 @@ static int build_lanes(vbc_handle *h, int w, const std::vector<Entry> &ents, con
     const std::vector<int32_t> &rrow = trow;  // one tile per range
     std::vector<int32_t> rchunk(nr + 1);
     for (int64_t r = 0; r <= nr; r++) rchunk[r] = (int32_t)r;
-    if (layout_knob("VBC_VERBOSE"))
+    if (h->verbose)
         fprintf(stderr, "[vbc] lanes bin w %d run %d pair %d stripes %lld ranges %lld x %lld stripes (target %d), rows "
                 "%lld (live %.3f)\n", w, run, (int)pair, (long long)nseg, (long long)nr, (long long)S, h->target_ranges_l,
                 (long long)rows, (double)real / (double)std::max<int64_t>(1, rows * NS * (run / rows_per_step)));
@@ -952,14 +962,11 @@ static int build_lanes(vbc_handle *h, int w, const std::vector<Entry> &ents, con
             }
         }
     }
-    h->slot_rows_padded += rows * NS * (run / rows_per_step);
-    h->slot_rows_real += real;
-    h->slot_rows_padded_last = rows * NS * (run / rows_per_step);
     return VBC_OK;
 }
 
 // One launch's slotted bins share one key form (the kernel is specialised on it).
-static void commit_launch_keys(const vbc_handle *h, std::vector<PendingSlot> &pss, Arena &ar)
+static void commit_launch_keys(const PlanCtx *h, std::vector<PendingSlot> &pss, Arena &ar)
 {
     bool kc = false;
     for (const PendingSlot &ps : pss) {
@@ -983,12 +990,12 @@ struct PendingSweep {
 // one slotted chunk folds together) span most of an x (length nx) too large for L2.  Mesh operators
 // span a few bandwidths (FE: ~10^4 rows of 10^7); the costs.jl:63-83 generator spans all of x.
 // Segment q's entries are ents[sbeg[q] .. sbeg[q+1]), keys = gather index.
-static bool sweep_possible(const vbc_handle *h, int w, int64_t nx)
+static bool sweep_possible(const PlanCtx *h, int w, int64_t nx)
 {
     return h->sweep_mode != 0 && w <= 8 && nx < kSlotIdxLimit && (h->sweep_mode == 1 || (double)nx * h->esz >= 16e6);
 }
 
-static bool want_sweep(const vbc_handle *h, int w, int64_t nx, const std::vector<int64_t> &sbeg,
+static bool want_sweep(const PlanCtx *h, int w, int64_t nx, const std::vector<int64_t> &sbeg,
                        const std::vector<Entry> &ents)
 {
     const int64_t nseg = (int64_t)sbeg.size() - 1;
@@ -1013,7 +1020,7 @@ static bool want_sweep(const vbc_handle *h, int w, int64_t nx, const std::vector
 // Segments per tile: as many as the wave's LDS tile holds (kind 0: w accumulators per stripe, kind 1:
 // one per output row).  Capping narrow buckets so that every tile costs the same measured slower on
 // the mixed-width NS workload (379 -> 395 us).
-static int sweep_segments(const vbc_handle *h, int kind, int w)
+static int sweep_segments(const PlanCtx *h, int kind, int w)
 {
     return (int)std::max(1, std::min(65535, h->sweep_tile / ((kind == 0 ? w : 1) * h->esz)));
 }
@@ -1021,7 +1028,7 @@ static int sweep_segments(const vbc_handle *h, int kind, int w)
 // Lay out a swept bucket: tiles of S segments; each tile's entries in 64-lane steps, taken in
 // ascending gather order by a min-heap over the segments' next entries (a segment enters a step at
 // most once, and its entries keep their stored order).  out[q] = y offset of segment q.
-static int build_sweep(vbc_handle *h, int kind, int w, const std::vector<int64_t> &sbeg,
+static int build_sweep(PlanCtx *h, int kind, int w, const std::vector<int64_t> &sbeg,
                        const std::vector<Entry> &ents, const std::vector<int32_t> &out, const char *val, Arena &ar,
                        int &tile0, PendingSweep &pw)
 {
@@ -1135,7 +1142,7 @@ static int build_sweep(vbc_handle *h, int kind, int w, const std::vector<int64_t
         if (voffs[e] >= 0) std::memcpy(vv + e * w * esz, val + voffs[e] * esz, (size_t)w * esz);
         else std::memset(vv + e * w * esz, 0, (size_t)w * esz);
     }
-    (kind == 0 ? h->bytes_t : h->bytes_f) +=
+    (kind == 0 ? h->st.bytes_t : h->st.bytes_f) +=
         E * ((packed ? 4 : 6) + (int64_t)w * esz) + (packed ? nsteps * 4 : 0) + (int64_t)tstep.size() * 4 +
         (b.out_affine ? 0 : nseg * 4);
     return VBC_OK;
@@ -1146,21 +1153,12 @@ static int build_sweep(vbc_handle *h, int kind, int w, const std::vector<int64_t
 // them with zero columns buys 16-B loads and the DPP scan for 14-60 % more value bytes.  The padding
 // columns multiply x[row] by 0 into outputs that are never written (the forward product, which would
 // gather x beyond the stripe, is never padded).  VBC_PAD="w:wp,..." overrides (A/B).
-static int padded_width(const vbc_handle *h, int w)
+static int padded_width(const PlanCtx *h, int w)
 {
     static const int def64[9] = {0, 1, 2, 4, 4, 5, 6, 8, 8};
     static const int def32[9] = {0, 1, 2, 4, 4, 5, 8, 8, 8};
     int wp = w <= 8 ? (h->esz == 8 ? def64[w] : def32[w]) : w;
-    if (const char *e = tuning_knob("VBC_PAD")) {
-        wp = w;
-        for (const char *p = e; *p;) {
-            int a = 0, b = 0, n = 0;
-            if (sscanf(p, "%d:%d%n", &a, &b, &n) != 2) break;
-            if (a == w && b >= w && b <= 64) wp = b;
-            p += n;
-            if (*p == ',') p++;
-        }
-    }
+    if (h->pad_set) wp = (w <= 64 && h->pad_w[w]) ? h->pad_w[w] : w;
     return wp;
 }
 
@@ -1171,7 +1169,7 @@ static int padded_width(const vbc_handle *h, int w)
 // stripe does not store never reaches it, as in the reference).  One key and one R-wide x gather per
 // run instead of one per row.  Fills hents / hsbeg (empty: no runs worth it).
 constexpr double kHoleFill = 0.15;
-static void hole_runs(const vbc_handle *h, const Stripes &s, const std::vector<int64_t> &stripes, int w,
+static void hole_runs(const PlanCtx *h, const Stripes &s, const std::vector<int64_t> &stripes, int w,
                       std::vector<Entry> &hents, std::vector<int64_t> &hsbeg)
 {
     hents.clear();
@@ -1214,7 +1212,7 @@ static void hole_runs(const vbc_handle *h, const Stripes &s, const std::vector<i
             }
             hsbeg.push_back((int64_t)hents.size());
         }
-        if (layout_knob("VBC_VERBOSE"))
+        if (h->verbose)
             fprintf(stderr, "[vbc] runs with holes: w %d R %d rows %lld -> %lld\n", w, R, (long long)real,
                     (long long)expanded);
         return;
@@ -1225,7 +1223,7 @@ static void hole_runs(const vbc_handle *h, const Stripes &s, const std::vector<i
 // boundaries into ks parts of equal run counts (the last may be shorter), the stripes by decreasing
 // length, 64 / ks of them per chunk, part p of the chunk's stripe i in lane p * (64 / ks) + i; lanes past
 // the last stripe hold empty segments.  ents[sbeg[q] ..] are stripe q's rows, out[q] its first column.
-static int build_ksplit(vbc_handle *h, int w, int ks, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
+static int build_ksplit(PlanCtx *h, int w, int ks, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
                         const std::vector<int32_t> &out, int64_t total, const char *val, Arena &ar, int &range0,
                         PendingSlot &ps)
 {
@@ -1257,7 +1255,7 @@ static int build_ksplit(vbc_handle *h, int w, int ks, const std::vector<Entry> &
                 const int64_t t = c * m + i;
                 order[c * 64 + p * m + i] = (t < n ? byl[t] : t) * ks + p;
             }
-    if (layout_knob("VBC_VERBOSE"))
+    if (h->verbose)
         fprintf(stderr, "[vbc] long stripes: w %d, %lld stripes cut into %d parts (runs of %d), %lld chunks\n", w,
                 (long long)n, ks, R, (long long)nchk);
     return build_slots(h, 0, w, w, ents, sx, ox, total, val, ar, range0, ps, order, false, ks);
@@ -1270,7 +1268,7 @@ static int build_ksplit(vbc_handle *h, int w, int ks, const std::vector<Entry> &
 // dependent loads at the loaded-memory latency of the streaming bucket beside it (42.6 us against the
 // strict partition's 33.8 us, profiles/r04_ab11_ldoor32_*.log).  Every output column keeps its
 // stripe's rows in stored order, so each column is summed exactly as before (multiply_1DVBC.jl:101-104).
-static bool column_pieces(const vbc_handle *h, const Stripes &s, Stripes &c)
+static bool column_pieces(const PlanCtx *h, const Stripes &s, Stripes &c)
 {
     if (h->colsplit == 0 || s.L < 1) return false;
     std::map<int, int64_t> cnt;
@@ -1308,7 +1306,7 @@ static bool column_pieces(const vbc_handle *h, const Stripes &s, Stripes &c)
         }
     }
     c.L = (int64_t)c.w.size();
-    if (layout_knob("VBC_VERBOSE"))
+    if (h->verbose)
         fprintf(stderr, "[vbc] column pieces: %lld stripes -> %lld (dominant width %d)\n", (long long)s.L,
                 (long long)c.L, wd);
     return true;
@@ -1317,7 +1315,7 @@ static bool column_pieces(const vbc_handle *h, const Stripes &s, Stripes &c)
 // Transposed layout: segments = stripes of each width, entries = their stored rows.  A bucket runs
 // slotted (vbc_slots.h, every stripe of the width a segment, empty ones included) when its row counts
 // are near-uniform, else merged (non-empty stripes; empty ones go to the fill list).
-static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, Arena &ar,
+static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Arena &ar,
                             std::vector<PendingBin> &pbs, std::vector<PendingSlot> &pss,
                             std::vector<PendingSweep> &pws, Launch &L, std::vector<int32_t> &fill)
 {
@@ -1334,8 +1332,8 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
     // chunks are too long to balance one wave each.  Taken when the chunks of all buckets together fill
     // at most half the wave slots (the split rule of build_slots) and every chunk keeps >= split_rows
     // (fp64) rows per wave; P is common to the launch.  VBC_SMALL_FUSE=0 turns it off.
-    h->small_split = 0;
-    h->fuse_w = 0;
+    h->st.small_split = 0;
+    h->st.fuse_w = 0;
     // A single-width small matrix runs the fused split when its bucket would otherwise take the merge
     // layout (chunks too long to balance one wave each: the 3dtube stand-in's 'overlap' partition, 15,110
     // 3-wide stripes of ~71 rows, fp64 16.4 -> 7.8 us, fp32 14.2 -> 6.8 us); a bucket the planar layouts
@@ -1374,7 +1372,7 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
             nall += c;
             if (c > nmax) { nmax = c; wmax = kv.first; }
         }
-        for (auto &kv : buckets) h->fuse_w |= 1u << kv.first;
+        for (auto &kv : buckets) h->st.fuse_w |= 1u << kv.first;
         // a dominant bucket headed for the merge layout is better fused too, up to one chunk per wave slot
         // (the ldoor stand-in's fp64 'min blocks', 2,358 chunks of 6-wide stripes of 69 rows: merge kernel
         // 131.5 us + the fused side launch 11.5 us; all fused 131.5 us, profiles/r04_ab17_ldoor64_blocks.log)
@@ -1382,8 +1380,8 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
                                merge_bound(wmax, buckets[wmax]);
         const bool side = h->side_fuse < 0 ? (double)nall * 2 > slots0 && buckets.size() >= 3 && (double)nmax >= 0.8 * (double)nall && !dom_merge
                                            : h->side_fuse == 1 && (double)nmax >= 0.8 * (double)nall;
-        if (side) h->fuse_w &= ~(1u << wmax);
-        auto fused_w = [&](int w) { return ((h->fuse_w >> w) & 1) != 0; };
+        if (side) h->st.fuse_w &= ~(1u << wmax);
+        auto fused_w = [&](int w) { return ((h->st.fuse_w >> w) & 1) != 0; };
         if (h->ksplit > 0) {
             double work = 0;
             int64_t nw = 0;
@@ -1448,15 +1446,15 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
                     if (eff(p) > eff(P) + 0.05) P = p;
             }
             if (h->planar_split > 1) P = h->planar_split;
-            if (P > 1) h->small_split = P;
+            if (P > 1) h->st.small_split = P;
         }
-        if (h->small_split <= 1) {
+        if (h->st.small_split <= 1) {
             kst.clear();
-            h->fuse_w = 0;
+            h->st.fuse_w = 0;
         }
-        if (layout_knob("VBC_VERBOSE"))
+        if (h->verbose)
             fprintf(stderr, "[vbc] small fused split: %d of %d buckets (width mask 0x%x), %lld chunks, %.1f rows per "
-                    "chunk -> P = %d%s\n", nf, (int)buckets.size(), h->fuse_w, (long long)nch, avg, h->small_split,
+                    "chunk -> P = %d%s\n", nf, (int)buckets.size(), h->st.fuse_w, (long long)nch, avg, h->st.small_split,
                     kst.empty() ? "" : ", long stripes cut");
     }
     // the bins: a width bucket, or (long stripes cut) its stripes of each part count ks
@@ -1503,7 +1501,7 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
         const int wp = padded_width(h, w);
         // the slotted kernel has no scan to feed: fp64 w = 3 runs unpadded (8-B lanes), measured
         // 117 -> 106 us on the ldoor stand-in (fp32 keeps 3 -> 4: 73 vs 84 us unpadded)
-        const int wps = slot_planar(h, 0, w) ? w : (h->esz == 8 && w == 3 && !tuning_knob("VBC_PAD")) ? 3 : wp;
+        const int wps = slot_planar(h, 0, w) ? w : (h->esz == 8 && w == 3 && !h->pad_set) ? 3 : wp;
         std::vector<int64_t> sbeg{0}, order;
         for (int64_t l : kv.second) sbeg.push_back(sbeg.back() + s.rbeg[l + 1] - s.rbeg[l]);
         bool mask = false;
@@ -1515,7 +1513,7 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
         // side bucket, a lane-stream or an unfused slotted / pair layout keeps the plain rows.
         std::vector<Entry> hents;
         std::vector<int64_t> hsbeg;
-        const bool fused_bucket = h->small_split > 1 && w <= 8 && ((h->fuse_w >> w) & 1) != 0;
+        const bool fused_bucket = h->st.small_split > 1 && w <= 8 && ((h->st.fuse_w >> w) & 1) != 0;
         if (fused_bucket && slot_planar(h, 0, w)) hole_runs(h, s, kv.second, w, hents, hsbeg);
         if (!hsbeg.empty()) {
             std::vector<int32_t> out0;
@@ -1583,35 +1581,35 @@ static int build_transposed(vbc_handle *h, const Stripes &s0, const char *val, A
         if (ents.empty()) continue;
         PendingBin pb;
         if (int st = build_bucket(h, 0, wp, ents, out, total, val, ar, range0, pb, w)) return st;
-        h->bytes_t += (int64_t)ents.size() * (4 + (int64_t)wp * h->esz) + (int64_t)out.size() * 4;
+        h->st.bytes_t += (int64_t)ents.size() * (4 + (int64_t)wp * h->esz) + (int64_t)out.size() * 4;
         pb.work = (double)ents.size() * (4.0 + (double)wp * h->esz);
         pbs.push_back(pb);
     }
     commit_launch_keys(h, pss, ar);
     for (const PendingSlot &ps : pss) {  // slotted bins: padded rows x (index bytes + values)
         if (ps.b.lanes) {  // lanes: real rows' values, one key per run, nlive per row, the tile tables
-            h->bytes_t += ps.real * (int64_t)ps.b.w * h->esz + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
+            h->st.bytes_t += ps.real * (int64_t)ps.b.w * h->esz + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
         } else if (ps.b.mask) {  // masked: padding lanes fetch nothing; + the per-row live counts
             const double f = (double)ps.real / (double)std::max<int64_t>(1, ps.rows * ps.b.rpi);
-            h->bytes_t += ps.real * (int64_t)ps.b.w * h->esz + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
+            h->st.bytes_t += ps.real * (int64_t)ps.b.w * h->esz + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
         } else {
-            h->bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
+            h->st.bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
         }
     }
     L.total_ranges = range0;
     L.slot_ranges = srange0;
     L.sweep_tiles = tile0;
-    L.fuse_p = h->small_split;  // (the handle's field is rebuilt by the next build_transposed call)
+    L.fuse_p = h->st.small_split;  // (the handle's field is rebuilt by the next build_transposed call)
     L.sweep_tile_bytes = h->sweep_tile;
-    if (const char *e = ablation_knob("VBC_SWEEP_DIAG")) L.sweep_diag = atoi(e);
-    h->bytes_t += (s.m + s.n) * h->esz;  // x read once, y written once
+    L.sweep_diag = h->sweep_diag;
+    h->st.bytes_t += (s.m + s.n) * h->esz;  // x read once, y written once
     return VBC_OK;
 }
 
 // Forward row runs (the forward counterpart of slot_runs): the largest R in {3, 2} such that the
 // output rows come in aligned runs of R (rows R*q .. R*q+R-1, m divisible by R) with identical stripe
 // lists -- the dof rows of a node in a stiffness operator.  sbeg: every row a segment (natural order).
-static int fwd_runs(const vbc_handle *h, int w, int64_t m, const std::vector<Entry> &ents,
+static int fwd_runs(const PlanCtx *h, int w, int64_t m, const std::vector<Entry> &ents,
                     const std::vector<int64_t> &sbeg)
 {
     if (h->slot_runs == 0 || h->slot_planar == 0 || w < 2 || w > 4 || m <= 0) return 1;
@@ -1637,7 +1635,7 @@ static int fwd_runs(const vbc_handle *h, int w, int64_t m, const std::vector<Ent
 // column-group-major over the chunk (planar_off with width R*w, element r*w + c); one key per block =
 // the stripe's first column (the gathered x slice).  Natural order: y offsets affine (R*q).
 // Returns false (and builds nothing) when the padded rows exceed slots_pad x the real ones.
-static bool build_fwd_runs(vbc_handle *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
+static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
                            int64_t m, const char *val, Arena &ar, int &range0, PendingSlot &ps)
 {
     const int esz = h->esz, RPI = 64, WV = R * w;
@@ -1705,7 +1703,7 @@ static bool build_fwd_runs(vbc_handle *h, int w, int R, const std::vector<Entry>
         }
     }
     rrow.push_back((int32_t)rows);
-    if (layout_knob("VBC_VERBOSE"))
+    if (h->verbose)
         fprintf(stderr, "[vbc] forward runs bin w %d R %d segments %lld chunks %lld rows %lld (real %lld) mask %d sorted %d "
                 "split %d ranges %zu\n", w, R, (long long)nseg, (long long)nch, (long long)rows, (long long)real, (int)mask,
                 (int)(!order.empty() && !mask), split, rchunk.size());
@@ -1776,8 +1774,6 @@ static bool build_fwd_runs(vbc_handle *h, int w, int R, const std::vector<Entry>
         }
     }
     ps.kc_ok = h->slot_keys16 != 0 && (split == 1 || h->split_kc) && slot_keys_compressible(ps.keys, rows, RPI);
-    h->slot_rows_padded += E;
-    h->slot_rows_real += real;
     (void)range0;
     return true;
 }
@@ -1789,7 +1785,7 @@ static bool build_fwd_runs(vbc_handle *h, int w, int R, const std::vector<Entry>
 // so the kernel folds acc[r] += A[R*q + r][j + d] * x[j + d] for d = 0..w-1, blocks in stripe order.
 // Chosen where the forward run layout would need the masked order (natural chunks pad beyond
 // slots_pad), with few empty segments and >= 256 segments per resident wave -- FE-3D.
-static bool want_fwd_lanes(const vbc_handle *h, int w, int R, int64_t m, const std::vector<int64_t> &sbeg)
+static bool want_fwd_lanes(const PlanCtx *h, int w, int R, int64_t m, const std::vector<int64_t> &sbeg)
 {
     if (h->planar_lanes == 0 || w < 1 || w > 3 || !slot_planar(h, 0, R) || m % R) return false;
     const int64_t nseg = m / R;
@@ -1807,7 +1803,7 @@ static bool want_fwd_lanes(const vbc_handle *h, int w, int R, int64_t m, const s
     return (double)nseg >= 256.0 * std::max(1, h->target_ranges_l);
 }
 
-static int build_fwd_lanes(vbc_handle *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
+static int build_fwd_lanes(PlanCtx *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
                            int64_t m, const char *val, Arena &ar, PendingSlot &ps)
 {
     const int esz = h->esz;
@@ -1842,7 +1838,7 @@ static int build_fwd_lanes(vbc_handle *h, int w, int R, const std::vector<Entry>
 // lane pair shares one 16-B gather per lane (ldoor stand-in fp64: its B'x in this layout runs 0.81 of the
 // HBM roofline, the forward row runs 0.69).  Returns kBuildDeclined (nothing built) when the bucket would not
 // take the pair layout (too few blocks per node, or a small matrix that takes the split product).
-static int build_fwd_pair(vbc_handle *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
+static int build_fwd_pair(PlanCtx *h, int w, int R, const std::vector<Entry> &ents, const std::vector<int64_t> &sbeg,
                           int64_t m, int64_t n, const char *val, Arena &ar, PendingSlot &ps)
 {
     if (h->esz != 8 || w != 3 || R != 3 || h->planar_pair == 0 || h->slot_planar == 0 || h->slot_runs == 0 || m % R)
@@ -1884,7 +1880,7 @@ static int build_fwd_pair(vbc_handle *h, int w, int R, const std::vector<Entry> 
 // of two or more widths (the forward layouts would need a scale pass plus one launch per width, each
 // adding into y), at most 2^23 stored rows, float eltypes, not VBC_CREATE_SERIAL (C sums each output over
 // B's columns in ascending order, not stripe by stripe), VBC_FWD_T != 0.
-static bool fwd_via_t_wanted(const vbc_handle *h, const Stripes &s, unsigned flags)
+static bool fwd_via_t_wanted(const PlanCtx *h, const Stripes &s, unsigned flags)
 {
     if (h->fwd_t == 0 || (flags & VBC_CREATE_SERIAL) || h->dtype == VBC_I64) return false;
     // a forced layout family (VBC_SLOTS / VBC_SWEEP / VBC_SLOT_PLANAR) keeps the forward layouts the tests ask for
@@ -1900,7 +1896,7 @@ static bool fwd_via_t_wanted(const vbc_handle *h, const Stripes &s, unsigned fla
     return mixed || h->fwd_t == 2;
 }
 
-static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena &ar,
+static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
                          std::vector<std::vector<PendingBin>> &pbs, std::vector<std::vector<PendingSlot>> &pss,
                          std::vector<std::vector<PendingSweep>> &pws, std::vector<Launch> &Ls,
                          std::vector<int32_t> &fill)
@@ -1933,12 +1929,12 @@ static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena
                 PendingSweep pw;
                 int tile0 = 0;
                 if (int st = build_sweep(h, 1, w, sb, ents, out, val, ar, tile0, pw)) return st;
-                h->bytes_f += s.m * h->esz;  // y written once per bucket
+                h->st.bytes_f += s.m * h->esz;  // y written once per bucket
                 std::fill(any.begin(), any.end(), 1);
                 Ls.emplace_back();
                 Ls.back().sweep_tiles = tile0;
                 Ls.back().sweep_tile_bytes = h->sweep_tile;
-                if (const char *e = ablation_knob("VBC_SWEEP_DIAG")) Ls.back().sweep_diag = atoi(e);
+                Ls.back().sweep_diag = h->sweep_diag;
                 pbs.push_back({});
                 pss.push_back({});
                 pws.push_back({pw});
@@ -1980,13 +1976,13 @@ static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena
                 commit_launch_keys(h, one, ar);
                 const PendingSlot &p1 = one[0];
                 if (lanes)  // real values, one key per block, nlive per row, the tile tables, y
-                    h->bytes_f += p1.real * (int64_t)R * h->esz + p1.key_bytes + p1.rows * 4 +
+                    h->st.bytes_f += p1.real * (int64_t)R * h->esz + p1.key_bytes + p1.rows * 4 +
                                   (int64_t)p1.b.ntiles * (8 + 128) + s.m * h->esz;
                 else if (fpair)  // run-rows of 32 blocks (288 values), one key per block, y
-                    h->bytes_f += p1.rows * 288 * (int64_t)h->esz + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
+                    h->st.bytes_f += p1.rows * 288 * (int64_t)h->esz + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
                                   s.m * h->esz;
                 else
-                    h->bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * h->esz + p1.key_bytes + s.m * h->esz;
+                    h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * h->esz + p1.key_bytes + s.m * h->esz;
                 std::fill(any.begin(), any.end(), 1);
                 pbs.push_back({});
                 pss.push_back(std::move(one));
@@ -2002,7 +1998,7 @@ static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena
             one.push_back(std::move(ps));
             commit_launch_keys(h, one, ar);
             const PendingSlot &p1 = one[0];
-            h->bytes_f += p1.rows * p1.b.rpi * (int64_t)w * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
+            h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
                           (int64_t)sout.size() * h->esz;
             for (int32_t i : sout) any[i] = 1;
             pbs.push_back({});
@@ -2017,18 +2013,18 @@ static int build_forward(vbc_handle *h, const Stripes &s, const char *val, Arena
         PendingBin pb;
         int range0 = 0;
         if (int st = build_bucket(h, 1, w, ents, out, (int64_t)ents.size(), val, ar, range0, pb)) return st;
-        h->bytes_f += (int64_t)ents.size() * (4 + (int64_t)w * h->esz) + (int64_t)out.size() * (4 + h->esz);
+        h->st.bytes_f += (int64_t)ents.size() * (4 + (int64_t)w * h->esz) + (int64_t)out.size() * (4 + h->esz);
         pbs.push_back({pb});
         pss.push_back({});
         pws.push_back({});
         Ls.back().total_ranges = range0;
     }
-    h->f_scale = buckets.size() > 1;
+    h->st.f_scale = buckets.size() > 1;
     if (buckets.size() <= 1)
         for (int64_t i = 0; i < s.m; i++)
             if (!any[i]) fill.push_back((int32_t)i);
-    if (h->f_scale) h->bytes_f += s.m * h->esz * 2 * (int64_t)buckets.size();
-    h->bytes_f += s.n * h->esz;
+    if (h->st.f_scale) h->st.bytes_f += s.m * h->esz * 2 * (int64_t)buckets.size();
+    h->st.bytes_f += s.n * h->esz;
     return VBC_OK;
 }
 
@@ -2102,7 +2098,7 @@ static std::vector<int64_t> cluster_ranges(int64_t nrg, const std::vector<int64_
     return order;
 }
 
-static bool build_tiles(vbc_handle *h, const Stripes &s, const std::vector<int64_t> &stripes_in, int w,
+static bool build_tiles(PlanCtx *h, const Stripes &s, const std::vector<int64_t> &stripes_in, int w,
                         const std::vector<int64_t> *tgrp, const char *val, Arena &ar, PendingPanel &pp)
 {
     const std::vector<int64_t> &stripes = stripes_in;  // (natural order)
@@ -2218,7 +2214,7 @@ static bool build_tiles(vbc_handle *h, const Stripes &s, const std::vector<int64
         nr = std::min<int64_t>(nr_cap, (nr + slots - 1) / slots * slots);
     }
     nr = std::min<int64_t>(n, nr);
-    if (const char *e = tuning_knob("VBC_TILE_RANGES")) nr = std::min<int64_t>(n, std::max<int64_t>(1, atoll(e)));
+    if (h->tile_ranges > 0) nr = std::min<int64_t>(n, h->tile_ranges);
     std::vector<int64_t> rb{0};  // range starts (stripe index)
     {
         int64_t cum = 0;
@@ -2274,7 +2270,7 @@ static bool build_tiles(vbc_handle *h, const Stripes &s, const std::vector<int64
     tb.ub = ub;
     tb.nbt = nbt;
     tb.depth = dep;
-    if (const char *e = ablation_knob("VBC_TILE_DIAG")) tb.diag = atoi(e);
+    tb.diag = h->tile_diag;
     {
         int64_t most = 1;
         for (size_t r = 0; r + 1 < rb.size(); r++) most = std::max<int64_t>(most, rb[r + 1] - rb[r]);
@@ -2359,8 +2355,8 @@ static bool build_tiles(vbc_handle *h, const Stripes &s, const std::vector<int64
         for (int64_t q = 0; q < nrg; q++) std::memcpy(dst + q * 8, &rinfo[(size_t)ord[q] * 8], 8 * sizeof(int32_t));
     }
     tb.masku = masku ? 1 : 0;
-    h->bytes_m += slot_total * (4 + (int64_t)TV * esz) + nrg * 32;
-    if (layout_knob("VBC_VERBOSE"))
+    h->st.bytes_m += slot_total * (4 + (int64_t)TV * esz) + nrg * 32;
+    if (h->verbose)
         fprintf(stderr, "[vbc] tiles: w %d, %lld stripes, %lld rows -> %lld tiles of <= %d rows (%s), %lld ranges, %lld slots%s%s\n",
                 w, (long long)n, (long long)rows, (long long)total, ub, R == 0 ? "block rows" : "row runs", (long long)nrg,
                 (long long)slot_total, masku ? ", masked rows" : "", cluster ? ", clustered launch order" : "");
@@ -2370,9 +2366,9 @@ static bool build_tiles(vbc_handle *h, const Stripes &s, const std::vector<int64
 // Panel layout (vbc_panel.h) of the transposed product: per width bucket (stripes wider than 16 are
 // cut into 16-column pieces that share the stripe's rows), S = 16/w consecutive stripes per panel,
 // each panel's rows padded to a multiple of 4, ranges of whole panels balanced by rows.
-static int build_panel(vbc_handle *h, const Stripes &s, const char *val, Arena &ar,
+static int build_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
                        std::vector<PendingPanel> &pps, PanelLaunch &L, std::vector<int32_t> &fill,
-                       const std::vector<int64_t> *tgrp = nullptr)
+                       const std::vector<int64_t> *tgrp)
 {
     struct Piece {
         int64_t l;
@@ -2453,7 +2449,7 @@ static int build_panel(vbc_handle *h, const Stripes &s, const char *val, Arena &
             pp.b.out_affine = (int64_t)out[q] == (int64_t)out[0] + (int64_t)q * pp.b.out_stride;
         const int64_t Rp = acc * 4;
         const int64_t Ra = Rp + kPanelTail;  // over-read padding (vbc_panel.h)
-        h->panel_val_bytes = std::max<int64_t>(h->panel_val_bytes, Ra * w * esz);
+        h->st.panel_val_bytes = std::max<int64_t>(h->st.panel_val_bytes, Ra * w * esz);
         pp.b.val_bytes = (int32_t)std::min<int64_t>(Ra * w * esz, 0x7FFFFFFF);
         pp.o_key = ar.reserve(Ra * 4);
         pp.o_val = ar.reserve(Ra * w * esz);
@@ -2490,7 +2486,7 @@ static int build_panel(vbc_handle *h, const Stripes &s, const char *val, Arena &
             key[row] = kPanelSentinel;
             std::memset(vv + row * w * esz, 0, (size_t)w * esz);
         }
-        h->bytes_m += Rp * (4 + (int64_t)w * esz) + (int64_t)out.size() * 4;
+        h->st.bytes_m += Rp * (4 + (int64_t)w * esz) + (int64_t)out.size() * 4;
         pps.push_back(pp);
     }
     L.total_ranges = range0;
@@ -2505,7 +2501,7 @@ static int build_panel(vbc_handle *h, const Stripes &s, const char *val, Arena &
 // Groups in row order, their stripes in stripe order (the reference's forward loop,
 // multiply_VBC.jl:68-77).  Every row of a group is stored by the same stripes, so C holds exactly the
 // values (fill zeros included) the reference multiplies.
-static int transpose_stripes(const vbc_handle *h, const Stripes &s, const char *val, int maxu, Stripes &c,
+static int transpose_stripes(const PlanCtx *h, const Stripes &s, const char *val, int maxu, Stripes &c,
                              std::vector<char> &cv)
 {
     const int esz = h->esz;
@@ -2588,7 +2584,7 @@ static int transpose_stripes(const vbc_handle *h, const Stripes &s, const char *
             for (int64_t q = b.q0; q < s.rbeg[l + 1] && gof[s.rows[q]] == b.g; q++) {
                 char *d = dst + (s.rows[q] - a[b.g]) * esz;
                 const char *v = val + (s.voff[l] + (q - s.rbeg[l]) * wl + cc) * esz;
-                if (g_rec) {  // a recording build: tags are copied, never summed, and a slot has one source
+                if (h->rec) {  // a recording build: tags are copied, never summed, and a slot has one source
                     static const char zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
                     if (std::memcmp(d, zero8, (size_t)esz) != 0)
                         return fail(VBC_INVALID_ARG, "a stripe stores one row twice: such a matrix cannot be "
@@ -2615,7 +2611,7 @@ static int transpose_stripes(const vbc_handle *h, const Stripes &s, const char *
 
 // Forward panel layout (VBC_CREATE_MULTI_FORWARD): Y = B·X is the transposed product of C = Bᵀ, so the
 // transposed panel layout of C (transpose_stripes, groups up to 16 rows) serves it.
-static int build_forward_panel(vbc_handle *h, const Stripes &s, const char *val, Arena &ar,
+static int build_forward_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
                                std::vector<PendingPanel> &pps, PanelLaunch &L)
 {
     Stripes c;
@@ -2624,17 +2620,28 @@ static int build_forward_panel(vbc_handle *h, const Stripes &s, const char *val,
     const int64_t ng = c.L;
     int32_t widest = 0;
     for (int64_t g = 0; g < ng; g++) widest = std::max(widest, c.w[g]);
-    h->mf_group = widest;
-    const int64_t bytes0 = h->bytes_m;
+    h->st.mf_group = widest;
+    const int64_t bytes0 = h->st.bytes_m;
     std::vector<int32_t> fill;
     // tile groups of C's rows (B's columns): B's stripes (Φ), so a u x w block of B is a w x u tile of C
     std::vector<int64_t> cg;
     for (int64_t l = 0; l < s.L; l++) cg.push_back(s.col0[l]);
     cg.push_back(s.n);
     const int st = build_panel(h, c, cv.data(), ar, pps, L, fill, &cg);
-    h->bytes_mf = h->bytes_m - bytes0;
-    h->bytes_m = bytes0;
+    h->st.bytes_mf = h->st.bytes_m - bytes0;
+    h->st.bytes_m = bytes0;
     return st;
+}
+
+
+// A bin table on the device.
+template <typename B>
+static int upload_bins(const std::vector<B> &bins, B *&d_bins)
+{
+    if (bins.empty()) return VBC_OK;
+    VBC_HIP(hipMalloc(&d_bins, bins.size() * sizeof(B)));
+    VBC_HIP(hipMemcpy(d_bins, bins.data(), bins.size() * sizeof(B), hipMemcpyHostToDevice));
+    return VBC_OK;
 }
 
 static int finalize_panel(vbc_handle *h, const std::vector<PendingPanel> &pps, PanelLaunch &L)
@@ -2661,15 +2668,11 @@ static int finalize_panel(vbc_handle *h, const std::vector<PendingPanel> &pps, P
         L.bins.push_back(b);
     }
     L.d_fill = reinterpret_cast<const int32_t *>(base + L.o_fill);
-    if (!L.bins.empty()) {
-        VBC_HIP(hipMalloc(&L.d_bins, L.bins.size() * sizeof(PanelBin)));
-        VBC_HIP(hipMemcpy(L.d_bins, L.bins.data(), L.bins.size() * sizeof(PanelBin), hipMemcpyHostToDevice));
-    }
-    return VBC_OK;
+    return upload_bins(L.bins, L.d_bins);
 }
 
 static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, const std::vector<PendingSlot> &pss,
-                           Launch &L, const std::vector<PendingSweep> &pws = {})
+                           Launch &L, const std::vector<PendingSweep> &pws)
 {
     L.bins.clear();
     L.sbins.clear();
@@ -2685,10 +2688,7 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         b.out = reinterpret_cast<const int32_t *>(base + pw.o_out);
         L.wbins.push_back(b);
     }
-    if (!L.wbins.empty()) {
-        VBC_HIP(hipMalloc(&L.d_wbins, L.wbins.size() * sizeof(SweepBin)));
-        VBC_HIP(hipMemcpy(L.d_wbins, L.wbins.data(), L.wbins.size() * sizeof(SweepBin), hipMemcpyHostToDevice));
-    }
+    if (int st = upload_bins(L.wbins, L.d_wbins)) return st;
     for (const PendingBin &pb : pbs) {
         Bin b = pb.b;
         b.key = reinterpret_cast<const uint32_t *>(base + pb.o_key);
@@ -2715,10 +2715,7 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         b.lseg = reinterpret_cast<const int16_t *>(base + ps.o_lseg);
         (b.planar ? L.pbins : L.sbins).push_back(b);
     }
-    if (!L.pbins.empty()) {
-        VBC_HIP(hipMalloc(&L.d_pbins, L.pbins.size() * sizeof(SlotBin)));
-        VBC_HIP(hipMemcpy(L.d_pbins, L.pbins.data(), L.pbins.size() * sizeof(SlotBin), hipMemcpyHostToDevice));
-    }
+    if (int st = upload_bins(L.pbins, L.d_pbins)) return st;
     // the fused small-matrix split (build_transposed): every planar bin a split bin of the common P, all
     // of them one launch of spmv_split_multi (their chunks concatenated)
     L.fuse_split = 0;
@@ -2750,14 +2747,8 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         }
     }
     L.d_fill = reinterpret_cast<const int32_t *>(base + L.o_fill);
-    if (!L.bins.empty()) {
-        VBC_HIP(hipMalloc(&L.d_bins, L.bins.size() * sizeof(Bin)));
-        VBC_HIP(hipMemcpy(L.d_bins, L.bins.data(), L.bins.size() * sizeof(Bin), hipMemcpyHostToDevice));
-    }
-    if (!L.sbins.empty()) {
-        VBC_HIP(hipMalloc(&L.d_sbins, L.sbins.size() * sizeof(SlotBin)));
-        VBC_HIP(hipMemcpy(L.d_sbins, L.sbins.data(), L.sbins.size() * sizeof(SlotBin), hipMemcpyHostToDevice));
-    }
+    if (int st = upload_bins(L.bins, L.d_bins)) return st;
+    if (int st = upload_bins(L.sbins, L.d_sbins)) return st;
     // bytes per launch group, in launch_group's order (sweep, slots, fused split, planar bins, merge)
     L.gwork.clear();
     {
@@ -2781,36 +2772,65 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
     return VBC_OK;
 }
 
+// Side streams for the independent groups of a transposed launch.
+static int fork_streams(const vbc_handle *h, Launch &Lx)
+{
+    if (!h->cfg.fork || launch_groups(Lx) < 2) return VBC_OK;
+    // no fork beside one dominant group when the others are more than a few waves of work: they are
+    // latency-bound, and beside a launch that saturates HBM their dependent loads wait on a loaded
+    // memory system while holding its wave slots (the ldoor stand-in's fp64 'min blocks': merge
+    // kernel 131.5 us + fused side launch 11.5 us one after another, 160.3 / 88.7 us side by side;
+    // 154 against 188 us per product, profiles/r04_bprof_*).  A side group of a few chunks still
+    // forks (its one wave hides under the big launch).
+    if ((int)Lx.gwork.size() == launch_groups(Lx)) {
+        double tot = 0, big = 0;
+        for (double wk : Lx.gwork) { tot += wk; big = std::max(big, wk); }
+        if (big >= 0.9 * tot && tot - big > h->cfg.fork_side_bytes) return VBC_OK;
+    }
+    const int ns = std::min(launch_groups(Lx) - 1, 3);
+    for (int i = 0; i < ns; i++) {
+        hipStream_t q = nullptr;
+        if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return fail(VBC_HIP_ERROR, "hipStreamCreate failed");
+        Lx.fork_streams.push_back(q);
+    }
+    for (int i = 0; i <= ns; i++) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(VBC_HIP_ERROR, "hipEventCreate failed");
+        Lx.fork_events.push_back(e);
+    }
+    return VBC_OK;
+}
+
+void Launch::free_device()
+{
+    if (d_bins) (void)hipFree(d_bins);
+    if (d_sbins) (void)hipFree(d_sbins);
+    if (d_wbins) (void)hipFree(d_wbins);
+    if (d_pbins) (void)hipFree(d_pbins);
+    for (hipStream_t q : fork_streams) (void)hipStreamDestroy(q);
+    for (hipEvent_t e : fork_events) (void)hipEventDestroy(e);
+}
+
+void PanelLaunch::free_device()
+{
+    if (d_bins) (void)hipFree(d_bins);
+}
+
 static void release(vbc_handle *h)
 {
     if (!h) return;
     DeviceGuard g(h->device);
-    if (h->lt.d_bins) (void)hipFree(h->lt.d_bins);
-    if (h->lt.d_sbins) (void)hipFree(h->lt.d_sbins);
-    if (h->lt.d_wbins) (void)hipFree(h->lt.d_wbins);
-    if (h->lt.d_pbins) (void)hipFree(h->lt.d_pbins);
-    if (h->lft.d_bins) (void)hipFree(h->lft.d_bins);
-    if (h->lft.d_sbins) (void)hipFree(h->lft.d_sbins);
-    if (h->lft.d_wbins) (void)hipFree(h->lft.d_wbins);
-    if (h->lft.d_pbins) (void)hipFree(h->lft.d_pbins);
-    for (hipStream_t q : h->lft.fork_streams) (void)hipStreamDestroy(q);
-    for (hipEvent_t e : h->lft.fork_events) (void)hipEventDestroy(e);
-    if (h->lm.d_bins) (void)hipFree(h->lm.d_bins);
-    if (h->lmf.d_bins) (void)hipFree(h->lmf.d_bins);
-    for (auto &l : h->lf) {
-        if (l.d_bins) (void)hipFree(l.d_bins);
-        if (l.d_sbins) (void)hipFree(l.d_sbins);
-        if (l.d_wbins) (void)hipFree(l.d_wbins);
-        if (l.d_pbins) (void)hipFree(l.d_pbins);
-    }
+    h->lft.free_device();
+    h->lm.free_device();
+    h->lmf.free_device();
+    for (Launch &l : h->lf) l.free_device();
     if (h->d_arena) (void)hipFree(h->d_arena);
     if (h->umap.d_buf) (void)hipFree(h->umap.d_buf);
     if (h->d_carry_mm) (void)hipFree(h->d_carry_mm);
     for (void *p : h->d_stage)
         if (p) (void)hipFree(p);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
-    for (hipStream_t q : h->lt.fork_streams) (void)hipStreamDestroy(q);
-    for (hipEvent_t e : h->lt.fork_events) (void)hipEventDestroy(e);
+    h->lt.free_device();
     delete h;
 }
 
@@ -2823,237 +2843,113 @@ static int64_t count_nonzeros(const char *val, int64_t n)
     return c;
 }
 
-// Integer eltypes: the reference layout itself (0-based) in one arena, read by vbc_generic.hip.
-static int create_int(vbc_handle *h, const Stripes &s, const int64_t *val, int64_t nval)
-{
+// Integer eltypes: arena offsets of IntLayout.
+struct IntPlan {
+    int64_t L = 0, nrows = 0;
+    size_t o_col0 = 0, o_w = 0, o_rows = 0, o_c2s = 0, o_r2s = 0, o_rbeg = 0, o_voff = 0, o_val = 0;
+};
+
+// What plan_layout makes and instantiate uploads: the arena image, per direction the pending bins (arena
+// offsets) and the host descriptors without device pointers -- transposed (t), forward as the transposed product
+// of C = Bᵀ (tf), forward with one launch per width bucket (f), panels (m, mf) -- and the statistics.
+struct Plan {
     Arena ar;
-    const int64_t L = s.L, q = (int64_t)s.rows.size();
-    const size_t o_col0 = ar.reserve(L * 4), o_w = ar.reserve(L * 4), o_rows = ar.reserve(q * 4);
-    const size_t o_c2s = ar.reserve(s.n * 4), o_r2s = ar.reserve(q * 4);
-    const size_t o_rbeg = ar.reserve((L + 1) * 8), o_voff = ar.reserve(L * 8), o_val = ar.reserve(nval * 8);
-    for (int64_t l = 0; l < L; l++) {
-        ar.at<int32_t>(o_col0)[l] = (int32_t)s.col0[l];
-        ar.at<int32_t>(o_w)[l] = s.w[l];
-        ar.at<int64_t>(o_voff)[l] = s.voff[l];
-        for (int64_t c = 0; c < s.w[l]; c++) ar.at<int32_t>(o_c2s)[s.col0[l] + c] = (int32_t)l;
-        for (int64_t r = s.rbeg[l]; r < s.rbeg[l + 1]; r++) ar.at<int32_t>(o_r2s)[r] = (int32_t)l;
-    }
-    std::memcpy(ar.at<int64_t>(o_rbeg), s.rbeg.data(), (L + 1) * 8);
-    if (q) std::memcpy(ar.at<int32_t>(o_rows), s.rows.data(), q * 4);
-    if (nval) std::memcpy(ar.at<int64_t>(o_val), val, nval * 8);
-    h->arena_bytes = h->arena_used = ar.host.size();
-    if (g_rec) {
-        g_rec->arena = std::move(ar.host);
-        return VBC_OK;
-    }
-    VBC_HIP(hipMalloc(&h->d_arena, h->arena_bytes));
-    VBC_HIP(hipMemcpy(h->d_arena, ar.host.data(), h->arena_bytes, hipMemcpyHostToDevice));
-    char *b = static_cast<char *>(h->d_arena);
-    IntLayout &li = h->li;
-    li.L = L;
-    li.nrows = q;
-    li.col0 = reinterpret_cast<const int32_t *>(b + o_col0);
-    li.w = reinterpret_cast<const int32_t *>(b + o_w);
-    li.rows = reinterpret_cast<const int32_t *>(b + o_rows);
-    li.col2stripe = reinterpret_cast<const int32_t *>(b + o_c2s);
-    li.row2stripe = reinterpret_cast<const int32_t *>(b + o_r2s);
-    li.rbeg = reinterpret_cast<const int64_t *>(b + o_rbeg);
-    li.voff = reinterpret_cast<const int64_t *>(b + o_voff);
-    li.val = reinterpret_cast<const int64_t *>(b + o_val);
-    h->bytes_t = h->bytes_f = nval * 8 + q * 4 + (s.m + s.n) * 8;
-    return VBC_OK;
-}
-
-static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtype, int device,
-                         unsigned flags, int64_t nval, int64_t K, int64_t nblocks)
-{
-    if (!out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
-    *out = nullptr;
-    if (dtype != VBC_F64 && dtype != VBC_F32 && dtype != VBC_I64)
-        return fail(VBC_UNSUPPORTED_DTYPE, "GPU products compute in Float64, Float32 or Int64 (see vbc_types)");
-    if (int st = check_limits(s)) return st;
-    int ndev = 0;
-    VBC_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VBC_INVALID_ARG, "device ordinal out of range");
-    if ((flags & (VBC_CREATE_TRANSPOSED | VBC_CREATE_FORWARD | VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD)) == 0)
-        flags |= VBC_CREATE_TRANSPOSED;
-
-    vbc_handle *h = new vbc_handle();
-    h->m = s.m;
-    h->n = s.n;
-    h->L = s.L;
-    h->K = K;
-    h->nblocks = nblocks;
-    h->nrows = (int64_t)s.rows.size();
-    h->nval = nval;
-    h->dtype = dtype;
-    h->esz = elem_size(dtype);
-    h->device = device;
-    h->narrow_values = g_narrow && dtype == VBC_F64;
-    const char *v = static_cast<const char *>(val);
-    h->nnz = dtype == VBC_F64 ? count_nonzeros<double>(v, nval)
-           : dtype == VBC_F32 ? count_nonzeros<float>(v, nval) : count_nonzeros<int64_t>(v, nval);
-
-    DeviceGuard g(device);
-    if (!g.ok) { release(h); return fail(VBC_HIP_ERROR, "hipSetDevice failed"); }
-    if (hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming) != hipSuccess) {
-        release(h);
-        return fail(VBC_HIP_ERROR, "hipEventCreate failed");
-    }
-    if (dtype == VBC_I64) {  // exact integer products (vbc_generic.hip): one layout, both directions
-        if (int st = create_int(h, s, static_cast<const int64_t *>(val), nval)) { release(h); return st; }
-        if (g_rec) { release(h); return VBC_OK; }
-        h->has_t = (flags & (VBC_CREATE_TRANSPOSED | VBC_CREATE_MULTI)) != 0;
-        h->has_f = (flags & (VBC_CREATE_FORWARD | VBC_CREATE_MULTI_FORWARD)) != 0;
-        *out = h;
-        return VBC_OK;
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { release(h); return fail(VBC_HIP_ERROR, "hipGetDeviceProperties failed"); }
-    h->tile_k = dtype == VBC_F64 ? 4 : 8;  // measured best (tools/ab.py, FE workload)
-    if (const char *e = tuning_knob("VBC_TILE_K")) {
-        const int k = atoi(e);
-        h->tile_k = (k == 4 || k == 8) ? k : h->tile_k;
-    }
-    if (const char *e = tuning_knob("VBC_PIPE")) h->pipe = atoi(e) == 3 ? 3 : 2;
-    if (const char *e = ablation_knob("VBC_DIAG")) h->diag = atoi(e);
-    // one range per resident wave: occupancy of the kernel variant this handle will launch
-    int occ[2] = {0, 0};
-    occupancy_ranges(h->esz, h->tile_k, h->pipe, occ);
-    for (int kd = 0; kd < 2; kd++)
-        h->target_ranges_k[kd] = prop.multiProcessorCount * std::max(1, std::min(occ[kd], 8)) * kWavesPerBlock;
-    if (const char *e = tuning_knob("VBC_TARGET_RANGES")) h->target_ranges_k[0] = h->target_ranges_k[1] = std::max(1, atoi(e));
-    for (int kd = 0; kd < 2; kd++) {
-        h->occ_s[kd] = std::max(1, std::min(occupancy_slots(h->esz, kd), 8));
-        h->target_ranges_s[kd] = prop.multiProcessorCount * h->occ_s[kd] * kWavesPerBlock;
-    }
-    if (const char *e = tuning_knob("VBC_TARGET_RANGES_S")) {  // an explicit range count is taken as is
-        h->target_ranges_s[0] = h->target_ranges_s[1] = std::max(1, atoi(e));
-        h->occ_s[0] = h->occ_s[1] = 1;
-    }
-    if (const char *e = layout_knob("VBC_RANGE_KB")) h->range_bytes = (int64_t)std::max(0, atoi(e)) << 10;
-    if (const char *e = layout_knob("VBC_SLOTS")) h->slots_mode = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;
-    if (const char *e = layout_knob("VBC_SLOTS_PAD")) h->slots_pad = atof(e);
-    if (const char *e = layout_knob("VBC_SLOTS_SORT")) h->slots_sort = atoi(e);
-    if (const char *e = tuning_knob("VBC_SLOT_NARROW")) h->slot_narrow = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_XCD")) h->xcd = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_XCD_P")) h->xcd_p = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_SLOT_KEYS16")) h->slot_keys16 = atoi(e);  // 0 off, 1 auto, 2 always
-    if (const char *e = layout_knob("VBC_SLOT_DEDUP")) h->slot_dedup = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_SWEEP")) h->sweep_mode = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;
-    h->sweep_tile = (h->esz == 8 ? 4 : 2) * kSweepTileBytes;  // measured on NS: fp64 32 KB 473 us (16 KB 508), fp32 16 KB 313 us (32 KB 353)
-    // packed swept keys: NS fp64 464.5 -> 456.2 us, mixed widths 553 -> 539 us; fp32 311 -> 316 us, so
-    // fp64 only (profiles/r03_sweeppack_*.log)
-    h->sweep_pack = h->esz == 8;
-    if (const char *e = layout_knob("VBC_FORK")) h->fork = atoi(e) != 0;
-    if (const char *e = tuning_knob("VBC_FORK_SIDE_KB")) h->fork_side_bytes = atof(e) * 1024.0;
-    if (const char *e = layout_knob("VBC_SWEEP_PACK")) h->sweep_pack = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_SWEEP_TILE")) h->sweep_tile = atoi(e) >= 32 ? 4 * kSweepTileBytes : atoi(e) >= 16 ? 2 * kSweepTileBytes : kSweepTileBytes;
-    if (const char *e = layout_knob("VBC_SLOT_STAGE")) h->slot_stage = (atoi(e) == 4 || atoi(e) == 8) ? atoi(e) : 0;
-    if (const char *e = layout_knob("VBC_SLOT_PLANAR")) h->slot_planar = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;
-    if (const char *e = layout_knob("VBC_SLOT_RUNS")) h->slot_runs = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_PLANAR_PAIR")) h->planar_pair = atoi(e) == 0 ? 0 : atoi(e) == 2 ? 2 : 1;  // 2: always
-    if (const char *e = layout_knob("VBC_PLANAR_MASK")) h->planar_mask = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_PLANAR_MASK_PAIR")) h->planar_mask_pair = atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_MASK_WINDOW")) h->mask_window = std::max(1, std::min(64, atoi(e)));
-    if (const char *e = layout_knob("VBC_PLANAR_SPLIT")) {  // 0 never, 1 auto, 2 / 4 / 8 forced
-        const int v = atoi(e);
-        h->planar_split = v == 0 ? 0 : (v == 2 || v == 4 || v == 8) ? v : -1;
-    }
-    if (flags & VBC_CREATE_SERIAL) {  // every stripe summed serially in stored row order:
-        h->planar_split = 0;            // no split planar product (P slices meeting in LDS),
-        if (h->slots_mode < 0) h->slots_mode = 1;  // and no merge layout (its segmented scan joins slot sums)
-    }
-    h->occ_p = std::max(1, std::min(occupancy_planar(h->esz), 8));
-    h->target_ranges_l = prop.multiProcessorCount * std::max(1, std::min(occupancy_lanes(h->esz), 8)) * kWavesPerBlock;
-    if (const char *e = layout_knob("VBC_PLANAR_LANES")) h->planar_lanes = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;
-    if (const char *e = layout_knob("VBC_TARGET_RANGES_L")) h->target_ranges_l = std::max(1, atoi(e));
-    if (const char *e = tuning_knob("VBC_LANES_DEEP")) h->lanes_deep = atoi(e) != 0;
-    if (const char *e = tuning_knob("VBC_LANES_RDIV")) h->lanes_rdiv = std::max(1, atoi(e));
-    if (const char *e = layout_knob("VBC_LANES_PAIR")) h->lanes_pair = atoi(e) != 0;
-    if (const char *e = tuning_knob("VBC_SPLIT_KC")) h->split_kc = atoi(e) != 0;
-    if (const char *e = tuning_knob("VBC_SPLIT_ROWS")) h->split_rows = std::max(1, atoi(e));
-    if (const char *e = layout_knob("VBC_SMALL_FUSE")) h->small_fuse = atoi(e);
-    if (const char *e = layout_knob("VBC_SIDE_FUSE")) h->side_fuse = atoi(e) < 0 ? -1 : atoi(e) != 0;
-    if (const char *e = layout_knob("VBC_COLSPLIT")) h->colsplit = atoi(e) != 0;
-    if (const char *e = tuning_knob("VBC_FUSE_PMAX")) h->fuse_pmax = atoi(e) >= 8 ? 8 : atoi(e) >= 4 ? 4 : 2;
-    if (const char *e = tuning_knob("VBC_COLSPLIT_W")) h->colsplit_w = std::max(0, atoi(e));
-    if (const char *e = tuning_knob("VBC_SPLIT_PIPE")) h->split_pipe = atoi(e);
-    if (const char *e = tuning_knob("VBC_SMALL_ROWS")) h->small_rows = std::max(1, atoi(e));
-    if (const char *e = layout_knob("VBC_KSPLIT")) h->ksplit = std::max(0.0, atof(e));
-    if (const char *e = layout_knob("VBC_FWD_T")) h->fwd_t = atoi(e);
-    if (const char *e = tuning_knob("VBC_SPLIT_DEEP")) h->split_deep = std::max(0.0, atof(e));
-    if (const char *e = tuning_knob("VBC_SPLIT_NT_MB")) h->split_nt_bytes = (int64_t)(atof(e) * (1 << 20));
-    if (const char *e = tuning_knob("VBC_FWD_MIN_ROWS")) h->fwd_min_rows = std::max(1, atoi(e));
-    if (const char *e = tuning_knob("VBC_PLANAR_WPS")) h->planar_wps = h->planar_wps_pair = std::max(0, atoi(e));
-    if (const char *e = tuning_knob("VBC_PLANAR_WPS_PAIR")) h->planar_wps_pair = std::max(0, atoi(e));
-    if (const char *e = tuning_knob("VBC_SLOT_WONLY")) h->slot_wonly = atoi(e) != 0;
-    h->target_ranges_p = prop.multiProcessorCount * h->occ_p * kWavesPerBlock;
-    h->cus = std::max(1, prop.multiProcessorCount);
-    for (int lp = 1; lp <= 3; lp++) h->occ_multi[lp] = occupancy_split_multi(h->esz, 1 << lp);
-    if (const char *e = tuning_knob("VBC_TARGET_RANGES_P")) {
-        h->target_ranges_p = std::max(1, atoi(e));
-        h->occ_p = 1;
-    }
-    h->slot_u = h->esz == 8 ? 8 : 16;  // rows per step (measured on FE: 4 / 8 rows are 4-8 % slower)
-    if (flags & (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD)) {
-        // (round 5: half as many ranges measured 195.5 against 206.5 us in tools/ab.py's interleaved graph replays,
-        // but 213-216 against 208-210 us in bench.py's own C5 line, each setting in a fresh process --
-        // profiles/r05zo_c5_ranges_ab.log; the bench decides, the count stays one round of resident waves)
-        const int om = occupancy_panel(h->esz);
-        h->target_ranges_m = prop.multiProcessorCount * std::max(1, std::min(om, 8)) * kWavesPerBlock;
-        if (const char *e = tuning_knob("VBC_TARGET_RANGES_M")) h->target_ranges_m = std::max(1, atoi(e));
-        if (const char *e = ablation_knob("VBC_PANEL_VALU")) h->panel_valu = atoi(e) != 0;
-        if (const char *e = ablation_knob("VBC_PANEL_DIAG")) h->panel_valu |= atoi(e) & ~1;
-        if (const char *e = tuning_knob("VBC_PANEL_NOBUF")) h->panel_nobuf = atoi(e) != 0;
-        if (const char *e = layout_knob("VBC_PANEL_TILES")) h->panel_tiles = atoi(e) < 0 ? -1 : atoi(e) != 0;
-        if (const char *e = tuning_knob("VBC_TILE_NBT")) h->tile_nbt = atoi(e) >= 8 ? 8 : 4;
-        if (const char *e = tuning_knob("VBC_TILE_SPR")) h->tile_spr = std::max(1, atoi(e));
-        if (const char *e = layout_knob("VBC_TILE_CLUSTER")) h->tile_cluster = atoi(e) == 2 ? 2 : atoi(e) != 0;
-        if (const char *e = tuning_knob("VBC_TILE_DEPTH")) h->tile_depth = atoi(e) == 3 ? 3 : 2;
-        h->occ_tiles = occupancy_tiles(h->esz);
-    }
-
-    Arena ar;
-    std::vector<PendingBin> pt;
-    std::vector<PendingSlot> st_t;
-    std::vector<PendingSweep> sw_t;
+    bool is_int = false;
+    IntPlan li;
+    std::vector<PendingBin> pt, ptf;
+    std::vector<PendingSlot> st_t, stf;
+    std::vector<PendingSweep> sw_t, swf;
     std::vector<std::vector<PendingBin>> pf;
     std::vector<std::vector<PendingSlot>> sf;
     std::vector<std::vector<PendingSweep>> wf;
-    std::vector<PendingPanel> pm;
-    std::vector<int32_t> fill_t, fill_f, fill_m;
+    std::vector<PendingPanel> pm, pmf;
+    Launch lt, lft;
+    std::vector<Launch> lf;
+    PanelLaunch lm, lmf;
+    PlanStats st;
+};
+
+static int check_plan_input(int dtype, const Stripes &s)
+{
+    if (dtype != VBC_F64 && dtype != VBC_F32 && dtype != VBC_I64)
+        return fail(VBC_UNSUPPORTED_DTYPE, "GPU products compute in Float64, Float32 or Int64 (see vbc_types)");
+    return check_limits(s);
+}
+
+// Integer eltypes: the reference layout itself (0-based) in one arena, read by vbc_generic.hip.
+static void plan_int(const Stripes &s, const int64_t *val, int64_t nval, Plan &P)
+{
+    Arena &ar = P.ar;
+    IntPlan &li = P.li;
+    const int64_t L = s.L, q = (int64_t)s.rows.size();
+    li.L = L;
+    li.nrows = q;
+    li.o_col0 = ar.reserve(L * 4), li.o_w = ar.reserve(L * 4), li.o_rows = ar.reserve(q * 4);
+    li.o_c2s = ar.reserve(s.n * 4), li.o_r2s = ar.reserve(q * 4);
+    li.o_rbeg = ar.reserve((L + 1) * 8), li.o_voff = ar.reserve(L * 8), li.o_val = ar.reserve(nval * 8);
+    for (int64_t l = 0; l < L; l++) {
+        ar.at<int32_t>(li.o_col0)[l] = (int32_t)s.col0[l];
+        ar.at<int32_t>(li.o_w)[l] = s.w[l];
+        ar.at<int64_t>(li.o_voff)[l] = s.voff[l];
+        for (int64_t c = 0; c < s.w[l]; c++) ar.at<int32_t>(li.o_c2s)[s.col0[l] + c] = (int32_t)l;
+        for (int64_t r = s.rbeg[l]; r < s.rbeg[l + 1]; r++) ar.at<int32_t>(li.o_r2s)[r] = (int32_t)l;
+    }
+    std::memcpy(ar.at<int64_t>(li.o_rbeg), s.rbeg.data(), (L + 1) * 8);
+    if (q) std::memcpy(ar.at<int32_t>(li.o_rows), s.rows.data(), q * 4);
+    if (nval) std::memcpy(ar.at<int64_t>(li.o_val), val, nval * 8);
+    P.st.bytes_t = P.st.bytes_f = nval * 8 + q * 4 + (s.m + s.n) * 8;
+}
+
+
+// The fill list of a launch (y entries no bin writes): into the arena, after the launch's bins.
+template <typename LaunchT>
+static void place_fill(Arena &ar, LaunchT &L, const std::vector<int32_t> &fill)
+{
+    L.nfill = (int)fill.size();
+    L.o_fill = ar.reserve(fill.size() * 4);
+    if (!fill.empty()) std::memcpy(ar.at<int32_t>(L.o_fill), fill.data(), fill.size() * 4);
+}
+
+// Plans every layout `flags` asks for (none of the four layout flags: the transposed one).  v: nval elements
+// of cfg.dtype.  Pure host code: no HIP call, no environment.
+static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v, int64_t nval, unsigned flags, Plan &P,
+                Recorder *rec)
+{
+    if (int st = check_plan_input(cfg.dtype, s)) return st;
+    if ((flags & (VBC_CREATE_TRANSPOSED | VBC_CREATE_FORWARD | VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD)) == 0)
+        flags |= VBC_CREATE_TRANSPOSED;
+    P = Plan{};
+    if (cfg.dtype == VBC_I64) {  // exact integer products (vbc_generic.hip): one layout, both directions
+        P.is_int = true;
+        plan_int(s, reinterpret_cast<const int64_t *>(v), nval, P);
+        P.st.has_t = (flags & (VBC_CREATE_TRANSPOSED | VBC_CREATE_MULTI)) != 0;
+        P.st.has_f = (flags & (VBC_CREATE_FORWARD | VBC_CREATE_MULTI_FORWARD)) != 0;
+        return VBC_OK;
+    }
+    PlanCtx ctx(cfg, P.st, rec, nval);
+    PlanCtx *h = &ctx;
+    Arena &ar = P.ar;
+    std::vector<int32_t> fill;
     int st = VBC_OK;
     if (flags & VBC_CREATE_MULTI) {
-        st = build_panel(h, s, v, ar, pm, h->lm, fill_m);
-        h->has_m = st == VBC_OK;
-        if (st == VBC_OK) {
-            h->lm.nfill = (int)fill_m.size();
-            h->lm.o_fill = ar.reserve(fill_m.size() * 4);
-            std::memcpy(ar.at<int32_t>(h->lm.o_fill), fill_m.data(), fill_m.size() * 4);
-        }
+        st = build_panel(h, s, v, ar, P.pm, P.lm, fill, nullptr);
+        h->st.has_m = st == VBC_OK;
+        if (st == VBC_OK) place_fill(ar, P.lm, fill);
     }
-    std::vector<PendingPanel> pmf;
     if (st == VBC_OK && (flags & VBC_CREATE_MULTI_FORWARD)) {
         const size_t c0 = ar.host.size();
-        st = build_forward_panel(h, s, v, ar, pmf, h->lmf);
-        if (g_rec) g_rec->canon.emplace_back(c0, ar.host.size());
-        h->has_mf = st == VBC_OK;
-        if (st == VBC_OK) h->lmf.o_fill = ar.reserve(4);
+        st = build_forward_panel(h, s, v, ar, P.pmf, P.lmf);
+        if (rec) rec->canon.emplace_back(c0, ar.host.size());
+        h->st.has_mf = st == VBC_OK;
+        if (st == VBC_OK) P.lmf.o_fill = ar.reserve(4);
     }
     if (st == VBC_OK && (flags & VBC_CREATE_TRANSPOSED)) {
-        st = build_transposed(h, s, v, ar, pt, st_t, sw_t, h->lt, fill_t);
-        h->has_t = st == VBC_OK;
-        if (st == VBC_OK) {
-            h->lt.nfill = (int)fill_t.size();
-            h->lt.o_fill = ar.reserve(fill_t.size() * 4);
-            std::memcpy(ar.at<int32_t>(h->lt.o_fill), fill_t.data(), fill_t.size() * 4);
-        }
+        fill.clear();
+        st = build_transposed(h, s, v, ar, P.pt, P.st_t, P.sw_t, P.lt, fill);
+        h->st.has_t = st == VBC_OK;
+        if (st == VBC_OK) place_fill(ar, P.lt, fill);
     }
-    std::vector<PendingBin> ptf;
-    std::vector<PendingSlot> stf;
-    std::vector<PendingSweep> swf;
-    std::vector<int32_t> fill_tf;
+    fill.clear();
     if (st == VBC_OK && (flags & VBC_CREATE_FORWARD) && fwd_via_t_wanted(h, s, flags)) {
         // small mixed-width forward product as the transposed product of C = Bᵀ (one fused launch instead
         // of a scale pass and one forward launch per width bucket, each adding into y)
@@ -3061,85 +2957,123 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
         std::vector<char> cv;
         st = transpose_stripes(h, s, v, 8, c, cv);
         if (st == VBC_OK) {
-            const int64_t bt = h->bytes_t;
+            const int64_t bt = h->st.bytes_t;
             const size_t c0 = ar.host.size();
             // (a stripe that stores one row twice had its copies summed in fp64: such values stay wide)
-            const bool nv = h->narrow_values;
-            h->narrow_values = nv && all_float_exact(cv.data(), (int64_t)(cv.size() / 8));
-            st = build_transposed(h, c, cv.data(), ar, ptf, stf, swf, h->lft, fill_tf);
-            h->narrow_values = nv;
-            if (g_rec) g_rec->canon.emplace_back(c0, ar.host.size());
-            h->bytes_f = h->bytes_t - bt;
-            h->bytes_t = bt;
+            LayoutConfig cfg_c = cfg;
+            cfg_c.narrow_values = cfg.narrow_values && all_float_exact(cv.data(), (int64_t)(cv.size() / 8));
+            PlanCtx hc(cfg_c, P.st, rec, nval);
+            st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
+            if (rec) rec->canon.emplace_back(c0, ar.host.size());
+            h->st.bytes_f = h->st.bytes_t - bt;
+            h->st.bytes_t = bt;
         }
         if (st == VBC_OK) {
-            h->has_f = h->has_ft = true;
-            h->lft.nfill = (int)fill_tf.size();
-            h->lft.o_fill = ar.reserve(fill_tf.size() * 4);
-            std::memcpy(ar.at<int32_t>(h->lft.o_fill), fill_tf.data(), fill_tf.size() * 4);
+            h->st.has_f = h->st.has_ft = true;
+            place_fill(ar, P.lft, fill);
         }
     } else if (st == VBC_OK && (flags & VBC_CREATE_FORWARD)) {
-        st = build_forward(h, s, v, ar, pf, sf, wf, h->lf, fill_f);
-        h->has_f = st == VBC_OK;
+        st = build_forward(h, s, v, ar, P.pf, P.sf, P.wf, P.lf, fill);
+        h->st.has_f = st == VBC_OK;
         if (st == VBC_OK) {
-            if (h->lf.empty()) h->lf.emplace_back();  // no entries: the fill list alone writes y
-            h->lf[0].nfill = (int)fill_f.size();
-            h->lf[0].o_fill = ar.reserve(fill_f.size() * 4);
-            std::memcpy(ar.at<int32_t>(h->lf[0].o_fill), fill_f.data(), fill_f.size() * 4);
+            if (P.lf.empty()) P.lf.emplace_back();  // no entries: the fill list alone writes y
+            place_fill(ar, P.lf[0], fill);
         }
     }
-    if (st != VBC_OK) { release(h); return st; }
-    h->arena_used = ar.host.size();
-    if (g_rec) {
-        g_rec->arena = std::move(ar.host);
-        release(h);
+    return st;
+}
+
+// What a create asks the device (the current one, ordinal `device`): the rows of the eltypes in `eltypes`
+// (bit 0: Float64, bit 1: Float32), the panel / tile rows only with `multi`.
+static int gather_facts(int device, unsigned eltypes, bool multi, DeviceFacts &f)
+{
+    f = DeviceFacts{};
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(VBC_HIP_ERROR, "hipGetDeviceProperties failed");
+    f.cus = prop.multiProcessorCount;
+    for (int e = 0; e < 2; e++) {
+        if (!((eltypes >> e) & 1)) continue;
+        const int esz = e ? 4 : 8;
+        for (int k = 0; k < 2; k++)
+            for (int p = 0; p < 2; p++) occupancy_ranges(esz, k ? 8 : 4, p ? 3 : 2, f.occ_ranges[e][k][p]);
+        for (int kd = 0; kd < 2; kd++) f.occ_slots[e][kd] = occupancy_slots(esz, kd);
+        f.occ_planar[e] = occupancy_planar(esz);
+        f.occ_lanes[e] = occupancy_lanes(esz);
+        for (int lp = 1; lp <= 3; lp++) f.occ_split_multi[e][lp - 1] = occupancy_split_multi(esz, 1 << lp);
+        if (multi) {
+            f.occ_panel[e] = occupancy_panel(esz);
+            f.occ_tiles[e] = occupancy_tiles(esz);
+        }
+    }
+    return VBC_OK;
+}
+
+// The device side of the handle: the caller's current device is `h->device`.
+static int instantiate_on_device(vbc_handle *h, Plan &P)
+{
+    if (hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming) != hipSuccess)
+        return fail(VBC_HIP_ERROR, "hipEventCreate failed");
+    const std::vector<char> &image = P.ar.host;
+    h->arena_used = image.size();
+    h->arena_bytes = P.is_int ? image.size() : std::max<size_t>(image.size(), 256);
+    if (hipMalloc(&h->d_arena, h->arena_bytes) != hipSuccess) return fail(VBC_HIP_ERROR, "hipMalloc of the matrix arena failed");
+    if (!image.empty() && hipMemcpy(h->d_arena, image.data(), image.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(VBC_HIP_ERROR, "hipMemcpy of the matrix arena failed");
+    if (P.is_int) {
+        const char *b = static_cast<const char *>(h->d_arena);
+        IntLayout &li = h->li;
+        li.L = P.li.L;
+        li.nrows = P.li.nrows;
+        li.col0 = reinterpret_cast<const int32_t *>(b + P.li.o_col0);
+        li.w = reinterpret_cast<const int32_t *>(b + P.li.o_w);
+        li.rows = reinterpret_cast<const int32_t *>(b + P.li.o_rows);
+        li.col2stripe = reinterpret_cast<const int32_t *>(b + P.li.o_c2s);
+        li.row2stripe = reinterpret_cast<const int32_t *>(b + P.li.o_r2s);
+        li.rbeg = reinterpret_cast<const int64_t *>(b + P.li.o_rbeg);
+        li.voff = reinterpret_cast<const int64_t *>(b + P.li.o_voff);
+        li.val = reinterpret_cast<const int64_t *>(b + P.li.o_val);
         return VBC_OK;
     }
-    h->arena_bytes = std::max<size_t>(ar.host.size(), 256);
-    if (hipMalloc(&h->d_arena, h->arena_bytes) != hipSuccess) {
-        release(h);
-        return fail(VBC_HIP_ERROR, "hipMalloc of the matrix arena failed");
-    }
-    if (!ar.host.empty() &&
-        hipMemcpy(h->d_arena, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        release(h);
-        return fail(VBC_HIP_ERROR, "hipMemcpy of the matrix arena failed");
-    }
-    if (h->has_t && (st = finalize_launch(h, pt, st_t, h->lt, sw_t))) { release(h); return st; }
-    if (h->has_ft && (st = finalize_launch(h, ptf, stf, h->lft, swf))) { release(h); return st; }
-    for (Launch *lp : {&h->lt, &h->lft}) {  // side streams for the independent groups of a transposed launch
-        Launch &Lx = *lp;
-        if (!(lp == &h->lt ? h->has_t : h->has_ft) || !h->fork || launch_groups(Lx) < 2) continue;
-        // no fork beside one dominant group when the others are more than a few waves of work: they are
-        // latency-bound, and beside a launch that saturates HBM their dependent loads wait on a loaded
-        // memory system while holding its wave slots (the ldoor stand-in's fp64 'min blocks': merge
-        // kernel 131.5 us + fused side launch 11.5 us one after another, 160.3 / 88.7 us side by side;
-        // 154 against 188 us per product, profiles/r04_bprof_*).  A side group of a few chunks still
-        // forks (its one wave hides under the big launch).
-        if ((int)Lx.gwork.size() == launch_groups(Lx)) {
-            double tot = 0, big = 0;
-            for (double wk : Lx.gwork) { tot += wk; big = std::max(big, wk); }
-            if (big >= 0.9 * tot && tot - big > h->fork_side_bytes) continue;
-        }
-        const int ns = std::min(launch_groups(Lx) - 1, 3);
-        for (int i = 0; i < ns; i++) {
-            hipStream_t q = nullptr;
-            if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) { release(h); return fail(VBC_HIP_ERROR, "hipStreamCreate failed"); }
-            Lx.fork_streams.push_back(q);
-        }
-        for (int i = 0; i <= ns; i++) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { release(h); return fail(VBC_HIP_ERROR, "hipEventCreate failed"); }
-            Lx.fork_events.push_back(e);
-        }
-    }
-    if (h->has_m && (st = finalize_panel(h, pm, h->lm))) { release(h); return st; }
-    if (h->has_mf && (st = finalize_panel(h, pmf, h->lmf))) { release(h); return st; }
-    for (size_t b = 0; b < pf.size(); b++)
-        if ((st = finalize_launch(h, pf[b], sf[b], h->lf[b], wf[b]))) { release(h); return st; }
-    if (h->has_f && !h->has_ft && pf.empty() && (st = finalize_launch(h, {}, {}, h->lf[0]))) { release(h); return st; }
+    h->lt = std::move(P.lt);
+    h->lft = std::move(P.lft);
+    h->lf = std::move(P.lf);
+    h->lm = std::move(P.lm);
+    h->lmf = std::move(P.lmf);
+    int st = VBC_OK;
+    if (h->has_t && (st = finalize_launch(h, P.pt, P.st_t, h->lt, P.sw_t))) return st;
+    if (h->has_ft && (st = finalize_launch(h, P.ptf, P.stf, h->lft, P.swf))) return st;
+    if (h->has_t && (st = fork_streams(h, h->lt))) return st;
+    if (h->has_ft && (st = fork_streams(h, h->lft))) return st;
+    if (h->has_m && (st = finalize_panel(h, P.pm, h->lm))) return st;
+    if (h->has_mf && (st = finalize_panel(h, P.pmf, h->lmf))) return st;
+    for (size_t b = 0; b < P.pf.size(); b++)
+        if ((st = finalize_launch(h, P.pf[b], P.sf[b], h->lf[b], P.wf[b]))) return st;
+    if (h->has_f && !h->has_ft && P.pf.empty() && (st = finalize_launch(h, {}, {}, h->lf[0], {}))) return st;
     h->has_scratch = (h->has_t && !h->lt.bins.empty()) || (h->has_ft && !h->lft.bins.empty());
     for (const Launch &l : h->lf) h->has_scratch = h->has_scratch || (h->has_f && !l.bins.empty());
+    return VBC_OK;
+}
+
+// Uploads a plan's arena to `device` and builds the handle around it (the caller fills the matrix dimensions).
+static int instantiate(Plan &P, const LayoutConfig &cfg, int device, vbc_handle **out)
+{
+    vbc_handle *h = new vbc_handle(cfg);
+    h->dtype = cfg.dtype;
+    h->esz = cfg.esz;
+    h->device = device;
+    h->cus = cfg.cus;
+    h->panel_nobuf = cfg.panel_nobuf;
+    h->has_t = P.st.has_t, h->has_f = P.st.has_f, h->has_ft = P.st.has_ft, h->has_m = P.st.has_m, h->has_mf = P.st.has_mf;
+    h->f_scale = P.st.f_scale;
+    h->bytes_t = P.st.bytes_t, h->bytes_f = P.st.bytes_f, h->bytes_m = P.st.bytes_m, h->bytes_mf = P.st.bytes_mf;
+    h->mf_group = P.st.mf_group;
+    h->panel_val_bytes = P.st.panel_val_bytes;
+    DeviceGuard g(device);
+    const int st = g.ok ? instantiate_on_device(h, P) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
+    if (st != VBC_OK) {
+        release(h);
+        return st;
+    }
     *out = h;
     return VBC_OK;
 }
@@ -3147,6 +3081,96 @@ static int create_common(vbc_handle **out, Stripes &s, const void *val, int dtyp
 }  // namespace vbc
 
 using namespace vbc;
+
+// The reference's fields as Stripes, with the checks of its inner constructors: shared by the creates and
+// vbcx_plan_image.  nval: the elements of val the stripes address.
+struct StripesInput {
+    Stripes s;
+    int64_t nval = 0, K = 0, nblocks = 0;
+};
+
+// A create after its entry's own checks.  build(v, in, val): the entry's stripes and the values they address,
+// from the caller's values (v = NULL) or from an array of the same shape (the recording plans below).
+// Order: the checks, the device's facts, the plan with the caller's values, the device part; then, for
+// VBC_CREATE_UPDATABLE, two recording plans of the same pattern on the host alone -- val all zero, val holding
+// the tag i + 1 in element i, written before any blocking or transposition of the values -- whose arenas differ
+// exactly in the value slots (vbc_update.hip build_value_map).
+template <typename F>
+static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags, bool narrow, F &&build)
+{
+    const bool updatable = (flags & VBC_CREATE_UPDATABLE) != 0;
+    flags &= ~VBC_CREATE_UPDATABLE;
+    if (updatable && !out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
+    if (updatable) *out = nullptr;
+    StripesInput in;
+    const void *val = nullptr;
+    if (int st = build(nullptr, in, val)) return st;
+    if (!out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
+    *out = nullptr;
+    if (int st = check_plan_input(dtype, in.s)) return st;
+    int ndev = 0;
+    VBC_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(VBC_INVALID_ARG, "device ordinal out of range");
+    const char *v = static_cast<const char *>(val);
+    const int64_t nval = in.nval;
+    DeviceFacts facts{};
+    if (dtype != VBC_I64) {
+        DeviceGuard g(device);
+        if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        if (int st = gather_facts(device, dtype == VBC_F64 ? 1u : 2u,
+                                  (flags & (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD)) != 0, facts))
+            return st;
+    }
+    const LayoutConfig cfg = make_config(dtype, flags, narrow, facts);
+    vbc_handle *h = nullptr;
+    {
+        Plan P;
+        if (int st = plan_layout(cfg, in.s, v, nval, flags, P, nullptr)) return st;
+        if (int st = instantiate(P, cfg, device, &h)) return st;
+    }
+    h->m = in.s.m;
+    h->n = in.s.n;
+    h->L = in.s.L;
+    h->K = in.K;
+    h->nblocks = in.nblocks;
+    h->nrows = (int64_t)in.s.rows.size();
+    h->nval = nval;
+    h->nnz = dtype == VBC_F64 ? count_nonzeros<double>(v, nval)
+           : dtype == VBC_F32 ? count_nonzeros<float>(v, nval) : count_nonzeros<int64_t>(v, nval);
+    if (!updatable) {
+        *out = h;
+        return VBC_OK;
+    }
+    const size_t esz = (size_t)h->esz;
+    int st = VBC_OK;
+    if (nval > kUpdMaxSource) st = fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
+    std::vector<char> arena[2];
+    Recorder rec;
+    std::vector<char> tv((size_t)std::max<int64_t>(nval, 1) * esz, 0);
+    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
+        if (pass == 1)
+            for (int64_t i = 0; i < nval; i++) {
+                const uint64_t tag = (uint64_t)i + 1;
+                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
+            }
+        rec = Recorder{};
+        Plan P;
+        if ((st = build(tv.data(), in, val)) == VBC_OK)
+            st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, &rec);
+        arena[pass] = std::move(P.ar.host);
+    }
+    tv = std::vector<char>();
+    if (st == VBC_OK && arena[0].size() != h->arena_used)
+        st = fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
+    if (st == VBC_OK) {
+        DeviceGuard g(h->device);
+        st = g.ok ? build_value_map(h, arena[1], arena[0], rec.canon) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
+    }
+    if (st != VBC_OK) { release(h); return st; }
+    h->updatable = true;
+    *out = h;
+    return VBC_OK;
+}
 
 extern "C" {
 
@@ -3163,48 +3187,17 @@ int vbc_last_error(char *buf, size_t n)
     return (int)g_err.size();
 }
 
-extern "C++" {
-// VBC_CREATE_UPDATABLE: the plain create (which validates everything and is the handle the caller gets), then
-// two recording builds of the same pattern -- val all zero, val holding the tag i + 1 in element i, written
-// before any blocking or transposition of the values -- whose arenas differ exactly in the value slots
-// (vbc_update.hip build_value_map).  create(out, val, nval): the entry point's own body; val = NULL: the caller's.
-template <typename F>
-static int create_updatable(vbc_handle **out, F &&create)
+
+int vbcx_device_facts(int device, vbcx_facts *out)
 {
-    if (!out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
-    *out = nullptr;
-    vbc_handle *h = nullptr;
-    if (int st = create(&h, nullptr, 0)) return st;
-    const int64_t nv = h->nval;
-    const size_t esz = (size_t)h->esz;
-    int st = VBC_OK;
-    if (nv > kUpdMaxSource) st = fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
-    MapRecorder rec[2];
-    std::vector<char> tv((size_t)std::max<int64_t>(nv, 1) * esz, 0);
-    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
-        if (pass == 1)
-            for (int64_t i = 0; i < nv; i++) {
-                const uint64_t tag = (uint64_t)i + 1;
-                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
-            }
-        vbc_handle *none = nullptr;
-        g_rec = &rec[pass];
-        st = create(&none, tv.data(), nv);
-        g_rec = nullptr;
-    }
-    tv = std::vector<char>();
-    if (st == VBC_OK && rec[0].arena.size() != h->arena_used)
-        st = fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
-    if (st == VBC_OK) {
-        DeviceGuard g(h->device);
-        st = g.ok ? build_value_map(h, rec[1].arena, rec[0].arena, rec[1].canon) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
-    }
-    if (st != VBC_OK) { release(h); return st; }
-    h->updatable = true;
-    *out = h;
-    return VBC_OK;
+    if (!out) return fail(VBC_INVALID_ARG, "NULL facts");
+    int ndev = 0;
+    VBC_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(VBC_INVALID_ARG, "device ordinal out of range");
+    DeviceGuard g(device);
+    if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
+    return gather_facts(device, 3u, true, *out);
 }
-}  // extern "C++"
 
 // VBC_CREATE_UPDATABLE_SHARDS belongs to the sharded creates (vbc_sharded.cpp), which pass VBC_CREATE_UPDATABLE on
 // to their shards; the plain and *_ex creates end here.
@@ -3223,9 +3216,9 @@ static int refuse_sharded_flag(vbc_handle **out)
     return fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE_SHARDS is a flag of the sharded creates (single handle: VBC_CREATE_UPDATABLE)");
 }
 
-static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
-                     const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                     int64_t nval, int dtype, int device, unsigned flags)
+
+static int stripes_1d(int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl, const int64_t *pos,
+               const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, StripesInput &in)
 {
     // SparseMatrix1DVBC{W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:45-50)
     if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
@@ -3234,7 +3227,8 @@ static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t 
     if (L < 0 || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad stripe arrays");
     if (spl[0] != 1 || spl[L] != n + 1) return fail(VBC_INVALID_ARG, "Φ.spl must run from 1 to n+1");
     if (pos[0] != 1 || ofs[0] != 1) return fail(VBC_INVALID_ARG, "pos[1] and ofs[1] must be 1");
-    Stripes s;
+    Stripes &s = in.s;
+    s = Stripes{};
     s.m = m; s.n = n; s.L = L;
     s.col0.resize(L); s.w.resize(L); s.rbeg.resize(L + 1); s.voff.resize(L);
     const int64_t q = pos[L] - 1;
@@ -3259,27 +3253,37 @@ static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t 
         if (idx[r] < 1 || idx[r] > m) return fail(VBC_INVALID_ARG, "idx out of range 1:m");
         s.rows[r] = (int32_t)(idx[r] - 1);
     }
-    return create_common(out, s, val, dtype, device, flags, ofs[L] - 1, 0, q);
+    in.nval = ofs[L] - 1;
+    in.K = 0;
+    in.nblocks = q;
+    return VBC_OK;
+}
+
+
+// `narrow`: VBC_CREATE_NARROW_VALUES as the *_ex creates checked it (they take it out of `flags`); the plain
+// creates pass false and refuse the flag.
+static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
+                     const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
+                     int64_t nval, int dtype, int device, unsigned flags, bool narrow)
+{
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
+        sv = v ? v : val;
+        return stripes_1d(m, n, W, L, spl, pos, idx, ofs, sv, nval, in);
+    });
 }
 
 int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
                  const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
                  int64_t nval, int dtype, int device, unsigned flags)
 {
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
-    if (!(flags & VBC_CREATE_UPDATABLE))
-        return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
-    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
-    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t nv) {
-        return create_1d(o, m, n, W, L, spl, pos, idx, ofs, v ? v : val, v ? nv : nval, dtype, device, f);
-    });
+    return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, false);
 }
 
-static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
-                     const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
-                     const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
-                     int device, unsigned flags)
+static int stripes_2d(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
+               const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
+               int64_t nval, StripesInput &in)
 {
     // SparseMatrixVBC{U,W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:72-79)
     if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
@@ -3304,7 +3308,8 @@ static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t 
     for (int64_t l = 0; l < L; l++)
         if (ofs[l + 1] < ofs[l]) return fail(VBC_INVALID_ARG, "ofs must be non-decreasing");
     if (ofs[L] - 1 > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
-    Stripes s;
+    Stripes &s = in.s;
+    s = Stripes{};
     s.m = m; s.n = n; s.L = L;
     s.col0.resize(L); s.w.resize(L); s.rbeg.resize(L + 1); s.voff.resize(L);
     // Expand every u×w tile into u stored rows with explicit x-row indices: the tile is already
@@ -3336,7 +3341,23 @@ static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t 
     }
     s.grp.resize(K + 1);
     for (int64_t k = 0; k <= K; k++) s.grp[k] = pspl[k] - 1;
-    return create_common(out, s, val, dtype, device, flags, ofs[L] - 1, K, q);
+    in.nval = ofs[L] - 1;
+    in.K = K;
+    in.nblocks = q;
+    return VBC_OK;
+}
+
+static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
+                     const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
+                     const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
+                     int device, unsigned flags, bool narrow)
+{
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
+        sv = v ? v : val;
+        return stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, sv, nval, in);
+    });
 }
 
 int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
@@ -3344,22 +3365,17 @@ int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, i
                  const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
                  int device, unsigned flags)
 {
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
-    if (!(flags & VBC_CREATE_UPDATABLE))
-        return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags);
-    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
-    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t nv) {
-        return create_2d(o, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, v ? v : val, v ? nv : nval, dtype, device, f);
-    });
+    return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, false);
 }
 
-static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
-                      const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
+// A SparseMatrixCSC as stripes.  bv: the values of the blocked stripes (sv then points into it).
+static int stripes_csc(int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const void *nzval,
+                       int dtype, StripesInput &in, std::vector<char> &bv, const void *&sv)
 {
     if (m < 0 || n < 0) return fail(VBC_INVALID_ARG, "number of rows/columns must be >= 0");
     if (!colptr || colptr[0] != 1) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
-    Stripes s;
+    Stripes &s = in.s;
+    s = Stripes{};
     s.m = m; s.n = n; s.L = n;
     s.col0.resize(n); s.w.assign(n, 1); s.rbeg.resize(n + 1); s.voff.resize(n);
     for (int64_t j = 0; j < n; j++) {
@@ -3399,7 +3415,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
             Stripes b;
             b.m = m; b.n = n; b.L = L;
             b.col0.resize(L); b.w.resize(L); b.rbeg.resize(L + 1); b.voff.resize(L);
-            std::vector<char> bv((size_t)std::max<int64_t>(nnz, 1) * esz);
+            bv.assign((size_t)std::max<int64_t>(nnz, 1) * esz, 0);
             const char *src = static_cast<const char *>(nzval);
             int64_t q = 0;
             for (int64_t l = 0; l < L; l++) {
@@ -3422,23 +3438,63 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
                 }
                 v += R * w;
             }
-            return create_common(out, b, bv.data(), dtype, device, flags, nnz, 0, q);
+            in.s = std::move(b);
+            in.nval = nnz;
+            in.K = 0;
+            in.nblocks = q;
+            sv = bv.data();
+            return VBC_OK;
         }
     }
-    return create_common(out, s, nzval, dtype, device, flags, nnz, 0, nnz);
+    in.nval = nnz;
+    in.K = 0;
+    in.nblocks = nnz;
+    sv = nzval;
+    return VBC_OK;
+}
+
+static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval,
+                      const void *nzval, int dtype, int device, unsigned flags, bool narrow)
+{
+    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    std::vector<char> bv;
+    // (the tags of an updatable create go into an nzval-shaped array, before the column blocking copies them)
+    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
+        return stripes_csc(m, n, colptr, rowval, v ? v : nzval, dtype, in, bv, sv);
+    });
 }
 
 int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                    const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
 {
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
-    if (!(flags & VBC_CREATE_UPDATABLE)) return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags);
-    const unsigned f = flags & ~VBC_CREATE_UPDATABLE;
-    // the tags go into an nzval-shaped array, before the column blocking below copies them into its stripes
-    return create_updatable(out, [&](vbc_handle **o, const void *v, int64_t) {
-        return create_csc(o, m, n, colptr, rowval, v ? v : nzval, dtype, device, f);
-    });
+    return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags, false);
+}
+
+int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
+                               const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
+                               const void *val, int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts,
+                               void *image, size_t capacity, size_t *bytes)
+{
+    if (!facts || !bytes) return fail(VBC_INVALID_ARG, "facts and bytes must not be NULL");
+    StripesInput in;
+    if (int st = pspl ? stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, in)
+                      : stripes_1d(m, n, W, L, spl, pos, idx, ofs, val, nval, in))
+        return st;
+    if (flags & (VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS))
+        return fail(VBC_INVALID_ARG, "vbcx_plan_image plans one layout: VBC_CREATE_UPDATABLE(_SHARDS) do not change it");
+    const bool narrow = (flags & VBC_CREATE_NARROW_VALUES) != 0;
+    if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
+    flags &= ~VBC_CREATE_NARROW_VALUES;
+    Plan P;
+    if (int st = plan_layout(make_config(dtype, flags, narrow, *facts), in.s, static_cast<const char *>(val), in.nval,
+                             flags, P, nullptr))
+        return st;
+    *bytes = P.ar.host.size();
+    if (!image) return VBC_OK;
+    if (capacity < *bytes) return fail(VBC_INVALID_ARG, "image buffer smaller than the arena image");
+    std::memcpy(image, P.ar.host.data(), *bytes);
+    return VBC_OK;
 }
 
 int vbc_destroy(vbc_handle *h)
@@ -3752,7 +3808,7 @@ static int convert_values(const void *val, int64_t nval, const vbc_types *t, std
 }
 
 // VBC_CREATE_NARROW_VALUES on an *_ex create: checked before any device work; the flag is then taken out of
-// `flags` and handed to create_common through NarrowScope.
+// `flags` and handed on as the creates' `narrow` argument.
 static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, bool &narrow)
 {
     narrow = false;
@@ -3815,9 +3871,8 @@ int vbc1d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L
     I.set(idx, t->index_bits, q);
     std::vector<char> cv;
     if (int st = convert_values(val, nval, t, cv)) return st;
-    NarrowScope ns(narrow);
-    return vbc1d_create(out, m, n, W, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval, t->compute_dtype,
-                        device, flags);
+    return create_1d(out, m, n, W, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval, t->compute_dtype,
+                     device, flags, narrow);
 }
 
 int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const void *pspl,
@@ -3838,9 +3893,8 @@ int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W
     I.set(idx, t->index_bits, q);
     std::vector<char> cv;
     if (int st = convert_values(val, nval, t, cv)) return st;
-    NarrowScope ns(narrow);
-    return vbc2d_create(out, m, n, U, W, K, PS.p, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval,
-                        t->compute_dtype, device, flags);
+    return create_2d(out, m, n, U, W, K, PS.p, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval,
+                     t->compute_dtype, device, flags, narrow);
 }
 
 int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr, const void *rowval,
@@ -3857,8 +3911,7 @@ int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr
     RV.set(rowval, t->index_bits, nnz);
     std::vector<char> cv;
     if (int st = convert_values(nzval, nnz, t, cv)) return st;
-    NarrowScope ns(narrow);
-    return vbc_csc_create(out, m, n, CP.p, RV.p, cv.empty() ? nzval : cv.data(), t->compute_dtype, device, flags);
+    return create_csc(out, m, n, CP.p, RV.p, cv.empty() ? nzval : cv.data(), t->compute_dtype, device, flags, narrow);
 }
 
 int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int64_t incx, int64_t nx, void *y, int y_dtype,

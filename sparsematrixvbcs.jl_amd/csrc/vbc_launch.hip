@@ -161,7 +161,7 @@ static int launch(const vbc_handle *h, const Launch &L, int kind, const void *x,
     const int G = launch_groups(L);
     const int nside = (int)L.fork_streams.size();
     if (kind != 0 || G < 2 || nside == 0)
-        return launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->xcd, h->slot_stage, -1);
+        return launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->cfg.xcd, h->cfg.slot_stage, -1);
     // fork: the side streams wait for the caller's stream; group 0 stays on it, group g >= 1 goes to
     // side stream (g - 1) % nside; every side stream that ran a group is joined back.  The event
     // sequence is serialised per handle (products on several caller streams at once).
@@ -185,7 +185,7 @@ static int launch(const vbc_handle *h, const Launch &L, int kind, const void *x,
         }
         if (!same) {
             (void)hipGetLastError();  // a refused query leaves no sticky error behind
-            return launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->xcd, h->slot_stage, -1);
+            return launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->cfg.xcd, h->cfg.slot_stage, -1);
         }
     }
     VBC_HIP(hipEventRecord(L.fork_events[0], stream));
@@ -200,8 +200,8 @@ static int launch(const vbc_handle *h, const Launch &L, int kind, const void *x,
     int st = VBC_OK, si = 0;
     for (int g = 0; g < G && st == VBC_OK; g++)
         if (g != gh)
-            st = launch_group<T>(L, kind, x, y, alpha, beta, rd, L.fork_streams[si++ % nside], h->xcd, h->slot_stage, g);
-    if (st == VBC_OK) st = launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->xcd, h->slot_stage, gh);
+            st = launch_group<T>(L, kind, x, y, alpha, beta, rd, L.fork_streams[si++ % nside], h->cfg.xcd, h->cfg.slot_stage, g);
+    if (st == VBC_OK) st = launch_group<T>(L, kind, x, y, alpha, beta, rd, stream, h->cfg.xcd, h->cfg.slot_stage, gh);
     for (int i = 0; i < used; i++) {  // joined even after a failed launch: no side stream is left dangling
         if (hipEventRecord(L.fork_events[1 + i], L.fork_streams[i]) != hipSuccess ||
             hipStreamWaitEvent(stream, L.fork_events[1 + i], 0) != hipSuccess) {

@@ -38,7 +38,7 @@ static int mulmat_panel(const vbc_handle *h, int trans, int64_t nrhs, const char
 #define VBC_PANEL(NB, BUF, FAST)                                                                              \
     hipLaunchKernelGGL((spmm_panel<T, NB, BUF, FAST>), dim3(grid), dim3(kBlockThreads), 0, s, L.d_bins,        \
                        (int)L.bins.size(), L.total_ranges, xs, sxr, sxc, xb, ys, syr, syc, yb, nr, (T)alpha, (T)beta, \
-                       (int)rd, h->panel_valu)
+                       (int)rd, h->cfg.panel_valu)
 #define VBC_PANEL_NB(BUF, FAST)                                                                               \
     do {                                                                                                      \
         if (nr <= 16) VBC_PANEL(1, BUF, FAST);                                                                \
