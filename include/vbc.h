@@ -28,7 +28,7 @@
  * vbc_sharded_update_values (vbc_info unchanged by both).  VBC_CREATE_NARROW_VALUES came without a version
  * bump (vbc_version() still returns 30400, no new symbol): a binding detects the capability by a create with
  * the flag succeeding and by vbc_info.planar_mask bits 12 / 13; a library without it refuses nothing and
- * never sets them. */
+ * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15. */
 #define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
@@ -126,6 +126,30 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       creates without vbc_types (their eltypes are equal), VBC_CREATE_UPDATABLE
                                       in the same call (the update kernel writes quads of the compute eltype),
                                       and both sharded creates. */
+
+#define VBC_CREATE_NARROW_PLANAR 0x100u /* Only together with VBC_CREATE_NARROW_VALUES (so on the *_ex creates with
+                                      Float32 values on a Float64 handle): the handle does everything 0x80 does and
+                                      also keeps Float32 values in the planar buckets the two plain planar kernels
+                                      run -- every B'x bucket in the chunk-planar layout of spmv_planar (one stripe
+                                      per lane: widths 3..8, row runs 1..3, masked or length-sorted order, 32-bit or
+                                      int16 keys, staged or direct y writes, not split) and every forward bucket of
+                                      spmv_planar_fwd (not split).  A narrow chunk row is stored in the Float32
+                                      column-group arrangement (16-B groups of four floats, the last group narrower),
+                                      so a lane's loads are those of the fp32 planar kernel; a lane holds its stripe's
+                                      whole row either way and widens each value as it folds it.  As with 0x80 no
+                                      layout decision changes and every product is bit-identical to that of the
+                                      handle created with 0x80 alone (and so to the wide handle's).  Buckets run by
+                                      any other planar kernel keep Float64 values: spmv_planar_pair, spmv_pair_lanes,
+                                      spmv_planar_lanes, spmv_planar_split, spmv_planar_fwd_split and the fused
+                                      spmv_split_multi; so do the swept, merge and panel / tile layouts.
+                                      vbc_info.planar_mask bit 14 / 15 say whether a B'x / forward planar bucket
+                                      stores Float32 (bits 12 / 13 keep meaning slotted buckets); bytes_t, bytes_f
+                                      and device_bytes count the bytes really stored.  Refused (VBC_INVALID_ARG, no
+                                      device work, no handle): 0x100 without 0x80, and every create that refuses 0x80
+                                      (the creates without vbc_types, any other eltype pair, VBC_CREATE_UPDATABLE in
+                                      the same call, both sharded creates).  No version bump and no new symbol, as
+                                      with 0x80: a binding detects the capability by bits 14 / 15; a library without
+                                      it ignores the bit. */
 
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
@@ -409,7 +433,9 @@ typedef struct vbc_info {
                                form); bit 11: the forward product of 3 x 3 fp64 node blocks in the lane-pair
                                layout of the transposed blocks (spmv_planar_pair DOT, round 6); bit 12: some
                                B'x slotted bucket stores Float32 values on this Float64 handle
-                               (VBC_CREATE_NARROW_VALUES), bit 13: some forward bucket does */
+                               (VBC_CREATE_NARROW_VALUES), bit 13: some forward bucket does; bit 14: some B'x
+                               planar bucket (spmv_planar) stores Float32 values (VBC_CREATE_NARROW_PLANAR),
+                               bit 15: some forward planar bucket (spmv_planar_fwd) does */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

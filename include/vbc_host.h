@@ -134,7 +134,8 @@ VBC_API int vbcx_device_facts(int device, vbcx_facts *out);
 
 /* The arena image a create with these arguments would upload under `facts` (needs no device): the fields of
  * vbc1d_create (pspl = NULL; U, K ignored) or vbc2d_create, checked as those do; dtype = the compute eltype of
- * val; flags = vbc_create_flags without VBC_CREATE_UPDATABLE(_SHARDS) (VBC_CREATE_NARROW_VALUES: val holds Float32 values widened to Float64).  The
+ * val; flags = vbc_create_flags without VBC_CREATE_UPDATABLE(_SHARDS) (VBC_CREATE_NARROW_VALUES, alone or with
+ * VBC_CREATE_NARROW_PLANAR: val holds Float32 values widened to Float64; 0x100 without 0x80 is refused).  The
  * environment knobs of INTEGRATION.md apply as in a create.  *bytes receives the image size; image = NULL
  * returns only that, else capacity must hold it. */
 VBC_API int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,

@@ -645,7 +645,11 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
     // VBC_CREATE_NARROW_VALUES: a slotted (non-planar) bin of an fp64 handle keeps its values as floats.  `val`
     // holds them widened (exactly), so narrowing gives the caller's bits back.  Only the stored size changes:
     // everything above was decided with esz.
-    const bool narrow = h->narrow_values && !planar && esz == 8;
+    // VBC_CREATE_NARROW_PLANAR: so does a chunk-planar bin the plain kernel runs (spmv_planar: not pair, not split
+    // -- which covers the fused small-matrix launch and runs with holes; lane streams are build_lanes'), its
+    // chunk rows in the Float32 column-group arrangement (planar_off(4, ...), rows of 64 * w floats: 16-B aligned)
+    const bool narrow = esz == 8 && (planar ? h->narrow_planar && !pair && split == 1 && !b.fused && !holes
+                                            : h->narrow_values);
     const int vsz = narrow ? 4 : esz;
     b.vsz = narrow ? 4 : 0;
     ps.o_val = ar.reserve(E * w * vsz * (pair ? 3 : 1));
@@ -725,14 +729,21 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
                     for (int d = 0; d < run; d++) mk |= (en[d].voff >= 0 ? 1u : 0u) << (kHoleShift + d);
                     key[e] |= mk;
                 }
-                if (planar) {  // column-group-major chunk row (vbc_planar.h)
-                    char *rowp = vv + row * RPI * w * esz;
+                if (planar) {  // column-group-major chunk row (vbc_planar.h), in the arrangement of the stored size
+                    char *rowp = vv + row * RPI * w * vsz;
                     for (int cc = 0; cc < w; cc++) {
-                        char *dst = rowp + planar_off(esz, w, sl, cc) * esz;
-                        if (real_row && cc < wsrc && en->voff >= 0) std::memcpy(dst, val + (en->voff + cc) * esz, (size_t)esz);
-                        else std::memset(dst, 0, (size_t)esz);
+                        char *dst = rowp + planar_off(vsz, w, sl, cc) * vsz;
+                        const bool stored = real_row && cc < wsrc && en->voff >= 0;
+                        if (stored && narrow) {
+                            const float f = (float)reinterpret_cast<const double *>(val)[en->voff + cc];
+                            std::memcpy(dst, &f, 4);
+                        } else if (stored) {
+                            std::memcpy(dst, val + (en->voff + cc) * esz, (size_t)esz);
+                        } else {
+                            std::memset(dst, 0, (size_t)vsz);
+                        }
                     }
-                } else if (narrow) {  // (never planar, so never a run with holes: voff >= 0)
+                } else if (narrow) {  // (slotted, so never a run with holes: voff >= 0)
                     float *dst = reinterpret_cast<float *>(vv) + e * w;
                     const double *src = reinterpret_cast<const double *>(val) + (real_row ? en->voff : 0);
                     for (int cc = 0; cc < w; cc++) dst[cc] = (real_row && cc < wsrc) ? (float)src[cc] : 0.0f;
@@ -1591,7 +1602,7 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
             h->st.bytes_t += ps.real * (int64_t)ps.b.w * h->esz + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
         } else if (ps.b.mask) {  // masked: padding lanes fetch nothing; + the per-row live counts
             const double f = (double)ps.real / (double)std::max<int64_t>(1, ps.rows * ps.b.rpi);
-            h->st.bytes_t += ps.real * (int64_t)ps.b.w * h->esz + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
+            h->st.bytes_t += ps.real * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
         } else {
             h->st.bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
         }
@@ -1735,7 +1746,12 @@ static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &e
     ps.real = real;
     if (mask) ps.o_nlive = ar.reserve((size_t)rows * 4);
     ps.keys.resize(E);
-    ps.o_val = ar.reserve(E * WV * esz);
+    // VBC_CREATE_NARROW_PLANAR (build_slots): the non-split bin (spmv_planar_fwd) stores floats, in the Float32
+    // column-group arrangement of width R * w; everything above was decided with esz
+    const bool narrow = h->narrow_planar && esz == 8 && split == 1;
+    const int vsz = narrow ? 4 : esz;
+    b.vsz = narrow ? 4 : 0;
+    ps.o_val = ar.reserve(E * WV * vsz);
     ps.o_out = ar.reserve(std::max<int64_t>(order.size(), 1) * 4);
     for (size_t p = 0; p < order.size(); p++) ar.at<int32_t>(ps.o_out)[p] = (int32_t)(R * order[p]);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
@@ -1747,7 +1763,7 @@ static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &e
     for (int64_t c = 0; c < nch; c++) {
         for (int32_t k = 0; k < cr[c]; k++, row++) {
             const uint32_t last = k + 1 == cr[c] ? kLast : 0u;
-            char *rowp = vv + row * RPI * WV * esz;
+            char *rowp = vv + row * RPI * WV * vsz;
             if (mask) {  // live lanes of this chunk row: a prefix in chunk-local length order
                 uint32_t nl = 0;
                 for (int sl = 0; sl < RPI; sl++) {
@@ -1766,9 +1782,15 @@ static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &e
                 ps.keys[e] = real_blk ? ((ents[sbeg[R * q] + k].key & kSlotIdx) | last) : (kPad | last);
                 for (int r = 0; r < R; r++)
                     for (int cc = 0; cc < w; cc++) {
-                        char *dst = rowp + planar_off(esz, WV, sl, r * w + cc) * esz;
-                        if (real_blk) std::memcpy(dst, val + (ents[sbeg[R * q + r] + k].voff + cc) * esz, (size_t)esz);
-                        else std::memset(dst, 0, (size_t)esz);
+                        char *dst = rowp + planar_off(vsz, WV, sl, r * w + cc) * vsz;
+                        if (real_blk && narrow) {
+                            const float f = (float)reinterpret_cast<const double *>(val)[ents[sbeg[R * q + r] + k].voff + cc];
+                            std::memcpy(dst, &f, 4);
+                        } else if (real_blk) {
+                            std::memcpy(dst, val + (ents[sbeg[R * q + r] + k].voff + cc) * esz, (size_t)esz);
+                        } else {
+                            std::memset(dst, 0, (size_t)vsz);
+                        }
                     }
             }
         }
@@ -1982,7 +2004,8 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                     h->st.bytes_f += p1.rows * 288 * (int64_t)h->esz + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
                                   s.m * h->esz;
                 else
-                    h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * h->esz + p1.key_bytes + s.m * h->esz;
+                    h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
+                                     s.m * h->esz;
                 std::fill(any.begin(), any.end(), 1);
                 pbs.push_back({});
                 pss.push_back(std::move(one));
@@ -2962,6 +2985,7 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
             // (a stripe that stores one row twice had its copies summed in fp64: such values stay wide)
             LayoutConfig cfg_c = cfg;
             cfg_c.narrow_values = cfg.narrow_values && all_float_exact(cv.data(), (int64_t)(cv.size() / 8));
+            cfg_c.narrow_planar = cfg.narrow_planar && cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
             st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
             if (rec) rec->canon.emplace_back(c0, ar.host.size());
@@ -3096,7 +3120,7 @@ struct StripesInput {
 // the tag i + 1 in element i, written before any blocking or transposition of the values -- whose arenas differ
 // exactly in the value slots (vbc_update.hip build_value_map).
 template <typename F>
-static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags, bool narrow, F &&build)
+static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags, unsigned narrow, F &&build)
 {
     const bool updatable = (flags & VBC_CREATE_UPDATABLE) != 0;
     flags &= ~VBC_CREATE_UPDATABLE;
@@ -3206,9 +3230,10 @@ static int refuse_narrow_flag(vbc_handle **out, const char *why)
     if (out) *out = nullptr;
     return fail(VBC_INVALID_ARG, why);
 }
-constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES needs Float32 values on a Float64 handle: pass it to "
-                                     "vbc1d_create_ex / vbc2d_create_ex / vbc_csc_create_ex (the creates without "
-                                     "vbc_types store the compute eltype)";
+constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR;
+constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR with it) needs Float32 values "
+                                     "on a Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
+                                     "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
 
 static int refuse_sharded_flag(vbc_handle **out)
 {
@@ -3260,14 +3285,14 @@ static int stripes_1d(int64_t m, int64_t n, int64_t W, int64_t L, const int64_t 
 }
 
 
-// `narrow`: VBC_CREATE_NARROW_VALUES as the *_ex creates checked it (they take it out of `flags`); the plain
-// creates pass false and refuse the flag.
+// `narrow`: the narrow-storage bits as the *_ex creates checked them (they take them out of `flags`); the plain
+// creates pass 0 and refuse both bits.
 static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
                      const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                     int64_t nval, int dtype, int device, unsigned flags, bool narrow)
+                     int64_t nval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
         sv = v ? v : val;
         return stripes_1d(m, n, W, L, spl, pos, idx, ofs, sv, nval, in);
@@ -3278,7 +3303,7 @@ int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, c
                  const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
                  int64_t nval, int dtype, int device, unsigned flags)
 {
-    return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, false);
+    return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, 0);
 }
 
 static int stripes_2d(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
@@ -3350,10 +3375,10 @@ static int stripes_2d(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, con
 static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
                      const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
                      const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
-                     int device, unsigned flags, bool narrow)
+                     int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
         sv = v ? v : val;
         return stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, sv, nval, in);
@@ -3365,7 +3390,7 @@ int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, i
                  const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
                  int device, unsigned flags)
 {
-    return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, false);
+    return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, 0);
 }
 
 // A SparseMatrixCSC as stripes.  bv: the values of the blocked stripes (sv then points into it).
@@ -3454,10 +3479,10 @@ static int stripes_csc(int64_t m, int64_t n, const int64_t *colptr, const int64_
 }
 
 static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval,
-                      const void *nzval, int dtype, int device, unsigned flags, bool narrow)
+                      const void *nzval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_VALUES) return refuse_narrow_flag(out, kNarrowPlain);
+    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     std::vector<char> bv;
     // (the tags of an updatable create go into an nzval-shaped array, before the column blocking copies them)
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
@@ -3468,7 +3493,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
 int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                    const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
 {
-    return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags, false);
+    return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags, 0);
 }
 
 int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
@@ -3483,9 +3508,11 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
         return st;
     if (flags & (VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS))
         return fail(VBC_INVALID_ARG, "vbcx_plan_image plans one layout: VBC_CREATE_UPDATABLE(_SHARDS) do not change it");
-    const bool narrow = (flags & VBC_CREATE_NARROW_VALUES) != 0;
+    const unsigned narrow = flags & kNarrowBits;
+    if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
-    flags &= ~VBC_CREATE_NARROW_VALUES;
+    flags &= ~kNarrowBits;
     Plan P;
     if (int st = plan_layout(make_config(dtype, flags, narrow, *facts), in.s, static_cast<const char *>(val), in.nval,
                              flags, P, nullptr))
@@ -3576,6 +3603,16 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     if (h->has_ft)
         for (const SlotBin &b : h->lft.sbins)
             if (b.vsz) info->planar_mask |= 1 << 13;
+    if (h->has_t)
+        for (const SlotBin &b : h->lt.pbins)
+            if (b.vsz) info->planar_mask |= 1 << 14;  // B'x planar buckets of Float32 values (VBC_CREATE_NARROW_PLANAR)
+    if (h->has_f)
+        for (const auto &l : h->lf)
+            for (const SlotBin &b : l.pbins)
+                if (b.vsz) info->planar_mask |= 1 << 15;  // forward ones
+    if (h->has_ft)
+        for (const SlotBin &b : h->lft.pbins)
+            if (b.vsz) info->planar_mask |= 1 << 15;
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3809,17 +3846,19 @@ static int convert_values(const void *val, int64_t nval, const vbc_types *t, std
 
 // VBC_CREATE_NARROW_VALUES on an *_ex create: checked before any device work; the flag is then taken out of
 // `flags` and handed on as the creates' `narrow` argument.
-static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, bool &narrow)
+static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, unsigned &narrow)
 {
-    narrow = false;
-    if (!(flags & VBC_CREATE_NARROW_VALUES)) return VBC_OK;
+    narrow = 0;
+    if (!(flags & kNarrowBits)) return VBC_OK;
+    if (!(flags & VBC_CREATE_NARROW_VALUES))
+        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES needs val_dtype VBC_F32 and compute_dtype VBC_F64");
     if (flags & VBC_CREATE_UPDATABLE)
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES cannot be combined with VBC_CREATE_UPDATABLE (the update "
                                        "kernel writes values of the compute eltype)");
-    flags &= ~VBC_CREATE_NARROW_VALUES;
-    narrow = true;
+    narrow = flags & kNarrowBits;
+    flags &= ~kNarrowBits;
     return VBC_OK;
 }
 
@@ -3859,7 +3898,7 @@ int vbc1d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L
                     unsigned flags)
 {
     if (int st = check_types(t)) return st;
-    bool narrow;
+    unsigned narrow;
     if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (L < 0 || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad stripe arrays");
     Idx64 S, P, I, O;
@@ -3880,7 +3919,7 @@ int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W
                     int64_t nval, const vbc_types *t, int device, unsigned flags)
 {
     if (int st = check_types(t)) return st;
-    bool narrow;
+    unsigned narrow;
     if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (K < 0 || L < 0 || !pspl || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad partition arrays");
     Idx64 PS, S, P, I, O;
@@ -3901,7 +3940,7 @@ int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr
                       const void *nzval, const vbc_types *t, int device, unsigned flags)
 {
     if (int st = check_types(t)) return st;
-    bool narrow;
+    unsigned narrow;
     if (int st = check_narrow(out, t, flags, narrow)) return st;
     if (n < 0 || !colptr) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
     Idx64 CP, RV;

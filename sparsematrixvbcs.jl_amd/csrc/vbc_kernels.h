@@ -136,7 +136,9 @@ struct SlotBin {
     int32_t dot;           // pair layout of a forward product (vbc_planar.h run_pair DOT): per block, each output
                            // row's dot product with the x slice is added to its sum (the reference's forward order)
     int32_t vsz;           // slotted: 4 = `val` holds Float32 values on an fp64 handle (VBC_CREATE_NARROW_VALUES:
-                           // widened in registers, every bin of the launch alike); 0 = values of the compute eltype
+                           // widened in registers, every bin of the launch alike); 0 = values of the compute eltype.
+                           // Planar (VBC_CREATE_NARROW_PLANAR; spmv_planar / spmv_planar_fwd bins only, never pair,
+                           // lanes or split): 4 = chunk rows in the Float32 column-group arrangement, planar_off(4, ..)
 };
 
 // Runs with holes (SlotBin::holes): the run's stored-row mask above the gather index of its first key.
@@ -215,7 +217,8 @@ constexpr int kWonlyNarrow2 = 102;  // spmv_slots WONLY: fp32 B'x w = 2 folded t
 int launch_slots(int esz, int vsz, int kind, const SlotBin *d_bins, int nbins, int total_ranges, bool faste, int xcd, int u, int diag, int stage, bool kc,
                  int wonly, const void *x, void *y, double alpha, double beta, bool rd, hipStream_t stream);
 int occupancy_slots(int esz, int kind);
-// vbc_planar.hip
+// vbc_planar.hip; a bin with vsz = 4 goes to the kernels of vbc_planar_f64n.hip (fp64 on Float32 stored values) or,
+// where there is none for its layout, fails with hipErrorInvalidValue
 int launch_planar(int esz, const SlotBin &hb, const SlotBin *d_b, bool faste, bool staged, const void *x, void *y,
                   double alpha, double beta, bool rd, hipStream_t s);
 int occupancy_planar(int esz);

@@ -167,14 +167,19 @@ __device__ __forceinline__ void xrun_values(const T (&r)[xrun_slots<T, RUN, PAIR
 // outputs): NB finished chunks staged in LDS and written as one run of 16-B stores.
 // MASK (SlotBin::mask): lanes >= nlive[row] are padding; they read lane 0's key and values (lines lane 0
 // fetches anyway) and fold nothing, so a chunk's padding rows cost no memory lines.
-template <typename T, int W_, int U, bool FASTE, int NB, bool KC, int RUN, bool MASK = false>
+// S: the stored value type (default T).  S = float with T = double (VBC_CREATE_NARROW_PLANAR): the chunk row
+// is stored in the Float32 column-group arrangement (planar_off(4, ...): groups of four floats), so a lane's
+// value loads are those of the fp32 kernel (ld_row<S>: 16 B, the tail group 12 / 8 / 4 B), the pipeline
+// registers hold floats and each value is widened (exactly) as the operand of its fmadd.  A lane holds its
+// stripe's whole row in either arrangement: U, the gathers, the fold order and the y writes stay those of T.
+template <typename T, int W_, int U, bool FASTE, int NB, bool KC, int RUN, bool MASK = false, typename S = T>
 __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, const T *__restrict__ x,
                                            T *__restrict__ y, T alpha, T beta, bool rd, char *lds_wave, int *lds_out)
 {
     const int R0 = G(b.rrow)[r], R1 = G(b.rrow)[r + 1];
     if (R0 >= R1) return;
     int c = G(b.rchunk)[r];
-    const gptr<const T> val = G(static_cast<const T *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const T> xg = G(x);
     typedef __attribute__((address_space(4))) const uint32_t *cptr;
@@ -183,7 +188,7 @@ __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, co
     const cptr nlive = (cptr)b.nlive;
     constexpr int NR = U / RUN;  // runs per step (ranges start and end on run boundaries)
     static_assert(NR * RUN == U, "a step holds whole runs");
-    auto load = [&](int R, uint32_t (&kk)[NR], uint32_t (&bs)[NR], int (&nl)[NR], T (&v)[U][W_]) {
+    auto load = [&](int R, uint32_t (&kk)[NR], uint32_t (&bs)[NR], int (&nl)[NR], S (&v)[U][W_]) {
 #pragma unroll
         for (int j = 0; j < NR; j++) {
             const int Rk = min(R + j * RUN, R1 - RUN);  // the run's first row (clamped: rows past the range)
@@ -202,7 +207,7 @@ __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, co
 #pragma unroll
             for (int d = 0; d < RUN; d++) {
                 const int Rc = min(R + j * RUN + d, R1 - 1);
-                ld_row<T, W_, 0>(val + (size_t)Rc * 64 * W_, ln, v[j * RUN + d]);
+                ld_row<S, W_, 0>(val + (size_t)Rc * 64 * W_, ln, v[j * RUN + d]);
             }
         }
     };
@@ -276,7 +281,7 @@ __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, co
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
     auto compute = [&](int R, const uint32_t (&kk)[NR], const uint32_t (&bs)[NR], const int (&nl)[NR],
-                       const T (&v)[U][W_], const T (&xv)[NR][xrun_slots<T, RUN>()]) {
+                       const S (&v)[U][W_], const T (&xv)[NR][xrun_slots<T, RUN>()]) {
 #pragma unroll
         for (int j = 0; j < NR; j++) {
             const bool pad = MASK ? lane >= nl[j] : (KC ? kk[j] == kPad16 : (kk[j] & kPad) != 0);
@@ -288,7 +293,7 @@ __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, co
                 const T xe = pad ? T(0) : xr[d];
 #pragma unroll
                 for (int e = 0; e < W_; e++) {
-                    const T nv = fmadd(v[j * RUN + d][e], xe, acc[e]);
+                    const T nv = fmadd((T)v[j * RUN + d][e], xe, acc[e]);
                     acc[e] = live ? nv : acc[e];
                 }
             }
@@ -298,7 +303,8 @@ __device__ __forceinline__ void run_planar(const SlotBin &b, int r, int lane, co
     };
     uint32_t kA[NR], kB[NR], bA[NR], bB[NR];
     int nA[NR], nB[NR];
-    T vA[U][W_], vB[U][W_], xv[NR][xrun_slots<T, RUN>()];
+    S vA[U][W_], vB[U][W_];
+    T xv[NR][xrun_slots<T, RUN>()];
     load(R0, kA, bA, nA, vA);
     __builtin_amdgcn_s_waitcnt(0);
     for (int R = R0; R < R1; R += 2 * U) {
@@ -339,7 +345,7 @@ __host__ __device__ constexpr int planar_nb()
     return (8192 / (64 * W_ * (int)sizeof(T))) > 8 ? 8 : (8192 / (64 * W_ * (int)sizeof(T)));
 }
 
-template <typename T, int W_, bool FASTE, int NB, bool KC, int RUN, bool MASK = false>
+template <typename T, int W_, bool FASTE, int NB, bool KC, int RUN, bool MASK = false, typename S = T>
 __global__ __launch_bounds__(kBlockThreads) void spmv_planar(const SlotBin b, const T *__restrict__ x,
                                                              T *__restrict__ y, T alpha, T beta, int rd_i)
 {
@@ -351,8 +357,8 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar(const SlotBin b, co
     char *lds = stage + (NB > 0 ? (threadIdx.x >> 6) * 8192 : 0);
     __shared__ int outs[FASTE ? 1 : kWavesPerBlock * kSlotOutEntries];
     int *lds_out = outs + (FASTE ? 0 : (threadIdx.x >> 6) * kSlotOutEntries);
-    run_planar<T, W_, planar_step<T, W_, RUN>(), FASTE, NB, KC, RUN, MASK>(b, rg, lane, x, y, alpha, beta, rd_i != 0,
-                                                                            lds, lds_out);
+    run_planar<T, W_, planar_step<T, W_, RUN>(), FASTE, NB, KC, RUN, MASK, S>(b, rg, lane, x, y, alpha, beta,
+                                                                               rd_i != 0, lds, lds_out);
 }
 
 // Per-lane compacted streams (SlotBin::lanes).  The masked chunk layout above steps every chunk
@@ -562,7 +568,9 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar_lanes(const SlotBin
 // serial stripe loop (:62-71).  At the LAST row the lane writes y[R*q .. R*q+R-1] (contiguous, LDS-
 // staged in runs of NB chunks when FASTE).
 // MASK (SlotBin::mask): lanes >= nlive[row] read lane 0's key and values and add nothing.
-template <typename T, int W_, int R, int U, bool FASTE, int NB, bool KC, bool MASK = false>
+// S: the stored value type (run_planar): a block's R x w values in the Float32 column-group arrangement of
+// width R*w, widened as the operands of the dot product.
+template <typename T, int W_, int R, int U, bool FASTE, int NB, bool KC, bool MASK = false, typename S = T>
 __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane, const T *__restrict__ x,
                                                T *__restrict__ y, T alpha, T beta, bool rd, char *lds_wave)
 {
@@ -570,14 +578,14 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
     const int R0 = G(b.rrow)[r], R1 = G(b.rrow)[r + 1];
     if (R0 >= R1) return;
     int c = G(b.rchunk)[r];
-    const gptr<const T> val = G(static_cast<const T *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const T> xg = G(x);
     typedef __attribute__((address_space(4))) const uint32_t *cptr;
     const cptr bases = (cptr)b.base;
     const cptr doffs = (cptr)b.kdoff;
     const cptr nlive = (cptr)b.nlive;
-    auto load = [&](int Rr, uint32_t (&kk)[U], uint32_t (&bs)[U], int (&nl)[U], T (&v)[U][WV]) {
+    auto load = [&](int Rr, uint32_t (&kk)[U], uint32_t (&bs)[U], int (&nl)[U], S (&v)[U][WV]) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int Rc = min(Rr + u, R1 - 1);
@@ -593,7 +601,7 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
                 kk[u] = __builtin_nontemporal_load(key + (size_t)Rc * 64 + ln);
                 bs[u] = 0;
             }
-            ld_row<T, WV, 0>(val + (size_t)Rc * 64 * WV, ln, v[u]);
+            ld_row<S, WV, 0>(val + (size_t)Rc * 64 * WV, ln, v[u]);
         }
     };
     constexpr uint32_t kPad16 = 0xFFFF8000u;
@@ -652,7 +660,7 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
     auto compute = [&](int Rr, const uint32_t (&kk)[U], const uint32_t (&bs)[U], const int (&nl)[U],
-                       const T (&v)[U][WV], const T (&xv)[U][xrun_slots<T, W_>()]) {
+                       const S (&v)[U][WV], const T (&xv)[U][xrun_slots<T, W_>()]) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const bool live = Rr + u < R1v;
@@ -661,9 +669,9 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
             xrun_values<T, W_>(xv[u], xr);
 #pragma unroll
             for (int q = 0; q < R; q++) {  // one dot product per output row of the run
-                T d = v[u][q * W_] * xr[0];
+                T d = (T)v[u][q * W_] * xr[0];
 #pragma unroll
-                for (int e = 1; e < W_; e++) d = fmadd(v[u][q * W_ + e], xr[e], d);
+                for (int e = 1; e < W_; e++) d = fmadd((T)v[u][q * W_ + e], xr[e], d);
                 acc[q] = (live && !pad) ? acc[q] + d : acc[q];
             }
             const uint32_t lastw = KC ? bs[u] : (uint32_t)__builtin_amdgcn_readfirstlane((int)kk[u]);
@@ -672,7 +680,8 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
     };
     uint32_t kA[U], kB[U], bA[U], bB[U];
     int nA[U], nB[U];
-    T vA[U][WV], vB[U][WV], xv[U][xrun_slots<T, W_>()];
+    S vA[U][WV], vB[U][WV];
+    T xv[U][xrun_slots<T, W_>()];
     load(R0, kA, bA, nA, vA);
     __builtin_amdgcn_s_waitcnt(0);
     for (int Rr = R0; Rr < R1; Rr += 2 * U) {
@@ -688,7 +697,7 @@ __device__ __forceinline__ void run_planar_fwd(const SlotBin &b, int r, int lane
     }
 }
 
-template <typename T, int W_, int R, bool FASTE, int NB, bool KC, bool MASK = false>
+template <typename T, int W_, int R, bool FASTE, int NB, bool KC, bool MASK = false, typename S = T>
 __global__ __launch_bounds__(kBlockThreads) void spmv_planar_fwd(const SlotBin b, const T *__restrict__ x,
                                                                  T *__restrict__ y, T alpha, T beta, int rd_i)
 {
@@ -703,7 +712,7 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar_fwd(const SlotBin b
 #endif
     // blocks per stage: ~VBC_FWD_VALS values per lane (fp64 R = 3, w = 3: 2 blocks)
     constexpr int U = (VBC_FWD_VALS / (R * W_)) < 2 ? 2 : (VBC_FWD_VALS / (R * W_));
-    run_planar_fwd<T, W_, R, U, FASTE, NB, KC, MASK>(b, rg, lane, x, y, alpha, beta, rd_i != 0, lds);
+    run_planar_fwd<T, W_, R, U, FASTE, NB, KC, MASK, S>(b, rg, lane, x, y, alpha, beta, rd_i != 0, lds);
 }
 
 // Split planar forward product (SlotBin kind 1, run = R, split = P > 1; ranges are single chunks of the

@@ -1,10 +1,15 @@
 // Launchers of the planar slotted kernel (vbc_planar.h): one launch per planar bucket, one kernel
-// instantiation per (value type, width 3..8, write path, key form, row run 1..3).
+// instantiation per (value type, width 3..8, write path, key form, row run 1..3).  The fp64 kernels on Float32
+// stored values (VBC_CREATE_NARROW_PLANAR) live in vbc_planar_f64n.hip.
 #include <hip/hip_runtime.h>
 
 #include "vbc_planar.h"
 
 namespace vbc {
+
+// vbc_planar_f64n.hip: spmv_planar / spmv_planar_fwd <double, ..., float> (bins with SlotBin::vsz = 4)
+int launch_planar_f64n(const SlotBin &hb, bool faste, bool staged, const void *x, void *y, double alpha, double beta,
+                       bool rd, hipStream_t s);
 
 template <typename T, int W_, bool KC, int RUN>
 static void launch_w(const SlotBin &hb, const SlotBin *d_b, bool faste, bool staged, const void *x, void *y,
@@ -224,6 +229,10 @@ int launch_planar(int esz, const SlotBin &hb, const SlotBin *d_b, bool faste, bo
                   double alpha, double beta, bool rd, hipStream_t s)
 {
     if (hb.nranges <= 0) return (int)hipSuccess;
+    if (hb.vsz) {  // Float32 stored values on an fp64 handle (VBC_CREATE_NARROW_PLANAR): vbc_planar_f64n.hip
+        if (esz != 8) return (int)hipErrorInvalidValue;
+        return launch_planar_f64n(hb, faste, staged, x, y, alpha, beta, rd, s);
+    }
     if (hb.lanes && hb.pair) {  // lane-pair streams (B'x, fp64, w = 3, runs of 3)
         if (hb.kind != 0 || esz != 8 || hb.wkey != 3 || hb.run != 3) return (int)hipErrorInvalidValue;
         const dim3 grid((hb.nranges + kWavesPerBlock - 1) / kWavesPerBlock), blk(kBlockThreads);

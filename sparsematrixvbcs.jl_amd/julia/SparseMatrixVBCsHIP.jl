@@ -86,8 +86,9 @@ Device-resident copies of `B`, one libvbc handle per compute eltype met (created
 `mul!`), freed by a finalizer (`vbc_destroy`).  The layout is immutable; with `updatable=true`
 (VBC_CREATE_UPDATABLE) `update_values!(M, val)` overwrites the stored values in place.  With `narrow=true`
 (VBC_CREATE_NARROW_VALUES) a Float32 matrix applied to Float64 vectors keeps its values as Float32 on the
-device (slotted buckets; same bits as without); for any other eltype pair the keyword is ignored.  `narrow`
-and `updatable` together throw an ArgumentError.
+device (slotted buckets; same bits as without); `narrow=:planar` (VBC_CREATE_NARROW_VALUES |
+VBC_CREATE_NARROW_PLANAR) also in the planar buckets of the plain planar kernels.  For any other eltype pair the
+keyword is ignored; any other value, or `narrow` and `updatable` together, throw an ArgumentError.
 """
 mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
     host::SparseMatrix1DVBC{W, Tv, Ti}
@@ -98,11 +99,10 @@ end
 
 function HIPSparseMatrix1DVBC(B::SparseMatrix1DVBC{W, Tv, Ti}; device::Integer=0, forward::Bool=true,
                               transposed::Bool=true, multi::Bool=false, updatable::Bool=false,
-                              narrow::Bool=false) where {W, Tv, Ti}
-    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
+                              narrow::Union{Bool, Symbol}=false) where {W, Tv, Ti}
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
             (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
-            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0))
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | narrow_flags(narrow, updatable)
     M = HIPSparseMatrix1DVBC{W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -127,11 +127,10 @@ end
 
 function HIPSparseMatrixVBC(B::SparseMatrixVBC{U, W, Tv, Ti}; device::Integer=0, forward::Bool=true,
                             transposed::Bool=true, multi::Bool=false, updatable::Bool=false,
-                            narrow::Bool=false) where {U, W, Tv, Ti}
-    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
+                            narrow::Union{Bool, Symbol}=false) where {U, W, Tv, Ti}
     flags = (transposed ? VBC_CREATE_TRANSPOSED : Cuint(0)) | (forward ? VBC_CREATE_FORWARD : Cuint(0)) |
             (multi ? (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD) : Cuint(0)) |
-            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0))
+            (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) | narrow_flags(narrow, updatable)
     M = HIPSparseMatrixVBC{U, W, Tv, Ti}(B, device, flags, Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -157,10 +156,9 @@ mutable struct HIPSparseMatrixCSC{Tv, Ti}
 end
 
 function HIPSparseMatrixCSC(A::SparseMatrixCSC{Tv, Ti}; device::Integer=0, updatable::Bool=false,
-                            narrow::Bool=false) where {Tv, Ti}
-    narrow && updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
+                            narrow::Union{Bool, Symbol}=false) where {Tv, Ti}
     M = HIPSparseMatrixCSC{Tv, Ti}(A, device, VBC_CREATE_TRANSPOSED | (updatable ? VBC_CREATE_UPDATABLE : Cuint(0)) |
-                                   (narrow ? VBC_CREATE_NARROW_VALUES : Cuint(0)),
+                                   narrow_flags(narrow, updatable),
                                    Dict{Cint, Ptr{Cvoid}}())
     finalizer(destroy_handles, M)
     return M
@@ -185,7 +183,8 @@ function handle_for(A::HIPMatrix, ::Type{Ty}) where {Ty}
     cdt = compute_dtype(Ty)
     cdt == VBC_I64 && eltype(A) <: AbstractFloat && throw(InexactError(:convert, Ty, zero(eltype(A))))
     # narrow values: only Float32 values on a Float64 handle (the library refuses the flag for any other pair)
-    flags = (eltype(A) === Float32 && cdt == VBC_F64) ? A.flags : A.flags & ~VBC_CREATE_NARROW_VALUES
+    flags = (eltype(A) === Float32 && cdt == VBC_F64) ? A.flags :
+            A.flags & ~(VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR)
     get!(() -> _create(A.host, A.device, flags, cdt), A.handles, cdt)
 end
 
@@ -279,6 +278,15 @@ const HIPShardedSparseMatrix1DVBC = HIPShardedSparseMatrix  # round-2 name
 const VBC_CREATE_SERIAL = Cuint(8)
 const VBC_CREATE_UPDATABLE = Cuint(0x20)
 const VBC_CREATE_NARROW_VALUES = Cuint(0x80)  # Float32 values kept narrow on a Float64 handle (slotted buckets)
+const VBC_CREATE_NARROW_PLANAR = Cuint(0x100)  # only with 0x80: the plain planar buckets too
+
+# the `narrow` keyword of the single-GPU constructors: false, true (0x80) or :planar (0x80 | 0x100)
+function narrow_flags(narrow, updatable::Bool)
+    narrow === false && return Cuint(0)
+    narrow === true || narrow === :planar || throw(ArgumentError("narrow must be false, true or :planar"))
+    updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
+    return narrow === true ? VBC_CREATE_NARROW_VALUES : VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR
+end
 const VBC_CREATE_UPDATABLE_SHARDS = Cuint(0x40)  # the sharded creates only (they refuse 0x20)
 
 _split_code(split) = split === :stripes ? VBC_SPLIT_STRIPES : split === :rows ? VBC_SPLIT_ROWS : VBC_SPLIT_AUTO

@@ -78,7 +78,9 @@ class _DeviceMatrix:
         serial per-stripe summation order whatever the size (vbc.h VBC_CREATE_SERIAL).
         Setting `B.narrow = True` before the first product keeps a float32 matrix's values as Float32 on
         the device when the product computes in Float64 (vbc.h VBC_CREATE_NARROW_VALUES: slotted buckets
-        only, products bit-identical); for any other eltype pair the attribute is ignored."""
+        only, products bit-identical); for any other eltype pair the attribute is ignored.
+        `B.narrow = "planar"` also keeps them narrow in the planar buckets of the plain planar kernels
+        (vbc.h VBC_CREATE_NARROW_PLANAR, passed together with 0x80); any other value raises ValueError."""
         if multi:  # matrix-core panels: of B for B'X, of Bᵀ for B·X
             flags = _L.VBC_CREATE_MULTI if trans else _L.VBC_CREATE_MULTI_FORWARD
         else:
@@ -92,12 +94,17 @@ class _DeviceMatrix:
             flags |= _L.VBC_CREATE_SERIAL  # the reference's serial per-stripe order in every layout
         if getattr(self, "updatable", False):
             flags |= _L.VBC_CREATE_UPDATABLE  # update_values rewrites the stored values in place
-        if getattr(self, "narrow", False):
+        narrow = getattr(self, "narrow", False)
+        if not (narrow is False or narrow is None or narrow is True or (isinstance(narrow, str) and narrow == "planar")):
+            raise ValueError("B.narrow must be False, True or 'planar', not %r" % (narrow,))
+        if narrow:
             if getattr(self, "updatable", False):
                 raise _L.ArgumentError("B.narrow and B.updatable cannot be combined (the update kernel writes "
                                        "values of the compute eltype)")
             if not multi and self._val.dtype == np.float32 and compute == _L.VBC_F64:
                 flags |= _L.VBC_CREATE_NARROW_VALUES  # Float32 values in HBM, widened in registers
+                if narrow == "planar":
+                    flags |= _L.VBC_CREATE_NARROW_PLANAR  # the plain planar buckets too
         return self._handles.get((int(device), flags, compute),
                                  lambda out: self._create(out, int(device), flags, compute))
 
@@ -111,6 +118,9 @@ class _DeviceMatrix:
         # derived keys (planar_mask bits 12 / 13): a B'x / forward slotted bucket stores Float32 values
         d["narrow_t"] = bool(inf.planar_mask & (1 << 12))
         d["narrow_f"] = bool(inf.planar_mask & (1 << 13))
+        # bits 14 / 15: a B'x / forward planar bucket does (VBC_CREATE_NARROW_PLANAR)
+        d["narrow_planar_t"] = bool(inf.planar_mask & (1 << 14))
+        d["narrow_planar_f"] = bool(inf.planar_mask & (1 << 15))
         return d
 
     def release(self):
