@@ -151,6 +151,32 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       with 0x80: a binding detects the capability by bits 14 / 15; a library without
                                       it ignores the bit. */
 
+#define VBC_CREATE_NARROW_UPDATABLE 0x200u /* Only together with VBC_CREATE_NARROW_VALUES, with or without
+                                      VBC_CREATE_NARROW_PLANAR (so on vbc1d_create_ex / vbc2d_create_ex /
+                                      vbc_csc_create_ex with Float32 values on a Float64 handle): the handle is the
+                                      narrow handle those bits give, plus a value map, and vbc_update_values works
+                                      on it.  The flag changes no layout decision: arena bytes, bytes_t, bytes_f,
+                                      every vbc_info field except device_bytes and every product are those of the
+                                      handle created with the same narrow bits and without 0x200; device_bytes adds
+                                      the map (4 bytes per stored value slot and the chunk table).  The map's
+                                      chunks carry their stored size, so one update kernel rewrites the Float32
+                                      buckets with Float32 quads and the Float64 buckets of the same handle (planar
+                                      buckets under 0x80 alone; pair, lane-stream, split, swept, merge buckets) with
+                                      widened values.  vbc_update_values on such a handle takes val_dtype == VBC_F32
+                                      only: a Float64 val would be rounded in the narrow buckets and kept exact in
+                                      the wide ones and leave a matrix no create produces, so any other known dtype
+                                      returns VBC_UNSUPPORTED_DTYPE before any work and the handle stays as it was.
+                                      Everything else is as documented at vbc_update_values.  Refused
+                                      (VBC_INVALID_ARG, no device work, no handle): 0x200 without 0x80, 0x200
+                                      together with VBC_CREATE_UPDATABLE (0x20), and every create that refuses 0x80
+                                      (the creates without vbc_types, any other eltype pair, both sharded creates
+                                      with or without VBC_CREATE_UPDATABLE_SHARDS).  0x80 | 0x20 stays refused as
+                                      before: callers and tests rely on that refusal, so the capability has its own
+                                      bit.  No version bump and no new product symbol, as with 0x80 and 0x100: a
+                                      binding detects the capability by the create succeeding and a following
+                                      vbc_update_values returning VBC_OK; a library without it ignores the bit and
+                                      its vbc_update_values returns VBC_INVALID_ARG. */
+
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
                                          X[i*ldx + j], ld >= nrhs); the fused multi-RHS kernel

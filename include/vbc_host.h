@@ -135,13 +135,40 @@ VBC_API int vbcx_device_facts(int device, vbcx_facts *out);
 /* The arena image a create with these arguments would upload under `facts` (needs no device): the fields of
  * vbc1d_create (pspl = NULL; U, K ignored) or vbc2d_create, checked as those do; dtype = the compute eltype of
  * val; flags = vbc_create_flags without VBC_CREATE_UPDATABLE(_SHARDS) (VBC_CREATE_NARROW_VALUES, alone or with
- * VBC_CREATE_NARROW_PLANAR: val holds Float32 values widened to Float64; 0x100 without 0x80 is refused).  The
+ * VBC_CREATE_NARROW_PLANAR: val holds Float32 values widened to Float64; 0x100 without 0x80 is refused;
+ * VBC_CREATE_NARROW_UPDATABLE is accepted together with 0x80 and changes nothing, and is refused without it).  The
  * environment knobs of INTEGRATION.md apply as in a create.  *bytes receives the image size; image = NULL
  * returns only that, else capacity must hold it. */
 VBC_API int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
                             const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
                             const void *val, int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts,
                             void *image, size_t capacity, size_t *bytes);
+
+/* One chunk of a value map: `n` 16-byte quads of stored value slots, `vsz` bytes each (0: the compute eltype's
+ * size, 4: Float32 slots of a narrow bucket), starting at slot `dst` of the arena image (in units of the chunk's
+ * stored size) and at entry `map` of the map. */
+typedef struct vbcx_map_chunk {
+    uint64_t dst;
+    uint64_t map;
+    uint32_t n;
+    uint32_t vsz;
+} vbcx_map_chunk;
+#define VBCX_MAP_ZERO 0xFFFFFFFFu  /* a padding slot: rewritten with zero */
+#define VBCX_MAP_SKIP 0xFFFFFFFEu  /* no value slot (a region's alignment to 16 bytes): never written */
+#define VBCX_MAP_CANON 0x80000000u /* with a source index: the slot holds 0 + v (-0 becomes +0) */
+
+/* The value map an updatable create with these arguments would keep under `facts` (needs no device; the creates
+ * run the same host code): the arguments of vbcx_plan_image, flags including VBC_CREATE_NARROW_VALUES [|
+ * VBC_CREATE_NARROW_PLANAR] where the handle would be created with VBC_CREATE_NARROW_UPDATABLE (the three
+ * UPDATABLE bits themselves are ignored).  One 32-bit entry per stored value slot, in arena order: the 0-based
+ * index of the source element of val, VBCX_MAP_CANON set where create stores 0 + v, or VBCX_MAP_ZERO /
+ * VBCX_MAP_SKIP.  *nentries and *nchunks are always written; a buffer is written only when it is not NULL and its
+ * capacity holds the count (call once with NULL buffers for the counts). */
+VBC_API int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
+                           const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
+                           const void *val, int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts,
+                           uint32_t *map, int64_t map_capacity, int64_t *nentries, vbcx_map_chunk *chunks,
+                           int64_t chunk_capacity, int64_t *nchunks);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,8 @@ VBC_CREATE_UPDATABLE = 0x20
 VBC_CREATE_UPDATABLE_SHARDS = 0x40  # the sharded creates only (they refuse 0x20)
 VBC_CREATE_NARROW_VALUES = 0x80  # *_ex creates, Float32 values on a Float64 handle only
 VBC_CREATE_NARROW_PLANAR = 0x100  # only together with 0x80: the plain planar buckets store Float32 too
-VBC_VERSION_MAJOR = 3  # include/vbc.h VBC_VERSION / 10000: the vbc_info layout below is that version's
+VBC_CREATE_NARROW_UPDATABLE = 0x200  # only together with 0x80 (never with 0x20): the narrow handle plus a value map
+VBC_VERSION_MAJOR = 3 # include/vbc.h VBC_VERSION / 10000: the vbc_info layout below is that version's
 VBC_INFO_SIZE = 152
 VBC_MUL_REFERENCE_QUIRKS = 0x1
 VBC_MAT_ROWMAJOR = 0x2
@@ -38,6 +39,7 @@ ABI_SYMBOLS = (
     "vbcx_partition_equi", "vbcx_partition_strict", "vbcx_partition_overlap",
     "vbcx_partition_dynamic", "vbcx_partition_dynamic_table", "vbcx_partition_block", "vbcx_1dvbc_count", "vbcx_1dvbc_fill", "vbcx_vbc_count",
     "vbcx_vbc_fill", "vbcx_transpose_pattern", "vbcx_sharded_value_plan", "vbcx_device_facts", "vbcx_plan_image",
+    "vbcx_value_map",
 )
 
 
@@ -82,6 +84,13 @@ class vbcx_facts(C.Structure):
                 ("occ_planar", C.c_int32 * 2), ("occ_lanes", C.c_int32 * 2), ("occ_split_multi", C.c_int32 * 3 * 2),
                 ("occ_panel", C.c_int32 * 2), ("occ_tiles", C.c_int32 * 2)]
 
+
+class vbcx_map_chunk(C.Structure):
+    """include/vbc_host.h vbcx_map_chunk: `n` 16-byte quads of value slots of `vsz` bytes (0: the compute eltype)."""
+    _fields_ = [("dst", C.c_uint64), ("map", C.c_uint64), ("n", C.c_uint32), ("vsz", C.c_uint32)]
+
+
+VBCX_MAP_ZERO, VBCX_MAP_SKIP, VBCX_MAP_CANON = 0xFFFFFFFF, 0xFFFFFFFE, 0x80000000
 
 _lib = None
 
@@ -150,6 +159,9 @@ def lib():
         L.vbcx_device_facts.argtypes = [INT, C.POINTER(vbcx_facts)]
         L.vbcx_plan_image.argtypes = [I64, I64, I64, I64, I64, P, I64, P, P, P, P, P, I64, INT, U, C.POINTER(vbcx_facts),
                                       P, C.c_size_t, C.POINTER(C.c_size_t)]
+        if hasattr(L, "vbcx_value_map"):  # (a host-only entry for tests and tools: a VBC_LIBRARY that predates it still loads)
+            L.vbcx_value_map.argtypes = [I64, I64, I64, I64, I64, P, I64, P, P, P, P, P, I64, INT, U, C.POINTER(vbcx_facts),
+                                         P, I64, C.POINTER(I64), P, I64, C.POINTER(I64)]
         _lib = L
     return _lib
 

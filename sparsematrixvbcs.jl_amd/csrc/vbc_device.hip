@@ -24,9 +24,14 @@ static thread_local std::string g_err;
 
 // The recorder of VBC_CREATE_UPDATABLE's recording plans (create_handle below): the byte ranges of the arena
 // filled from transpose_stripes' values (the value map marks their slots, vbc_handle.h).  With a recorder
-// transpose_stripes copies the (tag) values instead of summing them.
+// transpose_stripes copies the (tag) values instead of summing them.  `narrow`: the byte ranges of the value
+// regions stored as Float32 on a Float64 handle (VBC_CREATE_NARROW_UPDATABLE), in arena order; the builders that
+// narrow copy a tag's low 4 bytes there (narrow_value).  `ft_narrow`: whether the handle's own plan kept narrow
+// storage in the forward-on-Bᵀ layout (plan_layout's guard reads values, which a recording plan does not have).
 struct Recorder {
-    std::vector<std::pair<size_t, size_t>> canon;
+    ByteRanges canon;
+    ByteRanges narrow;
+    bool ft_narrow = false;
 };
 
 // What the builders write besides the arena: which layouts exist and their statistics.
@@ -36,6 +41,7 @@ struct PlanStats {
     int64_t bytes_t = 0, bytes_f = 0, bytes_m = 0, bytes_mf = 0;  // matrix bytes one product streams
     int32_t mf_group = 0;          // forward panel: widest output row group
     int64_t panel_val_bytes = 0;   // largest bin val array of the panel layout
+    bool ft_narrow = false;        // the forward-on-Bᵀ layout kept narrow storage (plan_layout's guard)
     // scratch of build_transposed, rebuilt by each call:
     int small_split = 0;           // > 1: this B'x layout is the fused small-matrix split with P waves per chunk
     uint32_t fuse_w = 0;           // bit w: the width-w bucket belongs to the fused split (all, or the side buckets)
@@ -60,6 +66,18 @@ static bool all_float_exact(const char *val, int64_t n)
         if (std::memcmp(&back, &d[i], 8) != 0) return false;
     }
     return true;
+}
+
+// The Float32 a narrow value slot stores for the fp64 value at `src`.  In a recording plan `src` holds a tag
+// (i + 1 <= 2^31 - 1 as an integer, a denormal as a double): its low 4 bytes are the tag and are never zero.
+static inline void narrow_value(const PlanCtx *h, const double *src, void *dst)
+{
+    if (h->rec) {
+        std::memcpy(dst, src, 4);  // little-endian
+    } else {
+        const float f = (float)*src;
+        std::memcpy(dst, &f, 4);
+    }
 }
 
 void set_error(const char *fmt, ...)
@@ -653,6 +671,7 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
     const int vsz = narrow ? 4 : esz;
     b.vsz = narrow ? 4 : 0;
     ps.o_val = ar.reserve(E * w * vsz * (pair ? 3 : 1));
+    if (narrow && h->rec) h->rec->narrow.emplace_back(ps.o_val, ps.o_val + (size_t)E * w * vsz);
     ps.o_out = ar.reserve(std::max<size_t>(out.size(), 1) * 4);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
     ps.o_rchunk = ar.reserve(rchunk.size() * 4);
@@ -735,8 +754,7 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
                         char *dst = rowp + planar_off(vsz, w, sl, cc) * vsz;
                         const bool stored = real_row && cc < wsrc && en->voff >= 0;
                         if (stored && narrow) {
-                            const float f = (float)reinterpret_cast<const double *>(val)[en->voff + cc];
-                            std::memcpy(dst, &f, 4);
+                            narrow_value(h, reinterpret_cast<const double *>(val) + en->voff + cc, dst);
                         } else if (stored) {
                             std::memcpy(dst, val + (en->voff + cc) * esz, (size_t)esz);
                         } else {
@@ -746,7 +764,10 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
                 } else if (narrow) {  // (slotted, so never a run with holes: voff >= 0)
                     float *dst = reinterpret_cast<float *>(vv) + e * w;
                     const double *src = reinterpret_cast<const double *>(val) + (real_row ? en->voff : 0);
-                    for (int cc = 0; cc < w; cc++) dst[cc] = (real_row && cc < wsrc) ? (float)src[cc] : 0.0f;
+                    for (int cc = 0; cc < w; cc++) {
+                        if (real_row && cc < wsrc) narrow_value(h, src + cc, dst + cc);
+                        else dst[cc] = 0.0f;
+                    }
                 } else if (real_row) {
                     std::memcpy(vv + e * w * esz, val + en->voff * esz, (size_t)wsrc * esz);
                     if (wsrc < w) std::memset(vv + (e * w + wsrc) * esz, 0, (size_t)(w - wsrc) * esz);
@@ -1752,6 +1773,7 @@ static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &e
     const int vsz = narrow ? 4 : esz;
     b.vsz = narrow ? 4 : 0;
     ps.o_val = ar.reserve(E * WV * vsz);
+    if (narrow && h->rec) h->rec->narrow.emplace_back(ps.o_val, ps.o_val + (size_t)E * WV * vsz);
     ps.o_out = ar.reserve(std::max<int64_t>(order.size(), 1) * 4);
     for (size_t p = 0; p < order.size(); p++) ar.at<int32_t>(ps.o_out)[p] = (int32_t)(R * order[p]);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
@@ -1784,8 +1806,7 @@ static bool build_fwd_runs(PlanCtx *h, int w, int R, const std::vector<Entry> &e
                     for (int cc = 0; cc < w; cc++) {
                         char *dst = rowp + planar_off(vsz, WV, sl, r * w + cc) * vsz;
                         if (real_blk && narrow) {
-                            const float f = (float)reinterpret_cast<const double *>(val)[ents[sbeg[R * q + r] + k].voff + cc];
-                            std::memcpy(dst, &f, 4);
+                            narrow_value(h, reinterpret_cast<const double *>(val) + ents[sbeg[R * q + r] + k].voff + cc, dst);
                         } else if (real_blk) {
                             std::memcpy(dst, val + (ents[sbeg[R * q + r] + k].voff + cc) * esz, (size_t)esz);
                         } else {
@@ -2983,9 +3004,14 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
             const int64_t bt = h->st.bytes_t;
             const size_t c0 = ar.host.size();
             // (a stripe that stores one row twice had its copies summed in fp64: such values stay wide)
+            // A recording plan holds tags, not values: it takes the answer the handle's own plan gave.  (That
+            // answer is always yes there -- a recording plan refuses a row stored twice, so every slot of cv is
+            // 0 + v of one widened float, which is a float -- but the plans must agree whatever it is.)
             LayoutConfig cfg_c = cfg;
-            cfg_c.narrow_values = cfg.narrow_values && all_float_exact(cv.data(), (int64_t)(cv.size() / 8));
+            cfg_c.narrow_values = cfg.narrow_values &&
+                                  (rec ? rec->ft_narrow : all_float_exact(cv.data(), (int64_t)(cv.size() / 8)));
             cfg_c.narrow_planar = cfg.narrow_planar && cfg_c.narrow_values;
+            h->st.ft_narrow = cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
             st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
             if (rec) rec->canon.emplace_back(c0, ar.host.size());
@@ -3119,10 +3145,49 @@ struct StripesInput {
 // VBC_CREATE_UPDATABLE, two recording plans of the same pattern on the host alone -- val all zero, val holding
 // the tag i + 1 in element i, written before any blocking or transposition of the values -- whose arenas differ
 // exactly in the value slots (vbc_update.hip build_value_map).
+
+// The two recording plans of an updatable create and the value map they give (vbc_update.hip value_map_host): pure
+// host code.  `ft_narrow`, `arena_used`: the forward-on-Bᵀ guard's answer and the image size of the plan made with
+// the caller's values, which the recording plans must reproduce.
+template <typename F>
+static int plan_value_map(const LayoutConfig &cfg, unsigned flags, StripesInput &in, F &&build, bool ft_narrow,
+                          size_t arena_used, std::vector<uint32_t> &map, std::vector<UpdChunk> &chunks)
+{
+    const int64_t nval = in.nval;
+    const size_t esz = (size_t)cfg.esz;
+    if (nval > kUpdMaxSource)
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
+    int st = VBC_OK;
+    std::vector<char> arena[2];
+    Recorder rec;
+    std::vector<char> tv((size_t)std::max<int64_t>(nval, 1) * esz, 0);
+    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
+        if (pass == 1)
+            for (int64_t i = 0; i < nval; i++) {
+                const uint64_t tag = (uint64_t)i + 1;
+                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
+            }
+        rec = Recorder{};
+        rec.ft_narrow = ft_narrow;
+        Plan P;
+        const void *val = nullptr;
+        if ((st = build(tv.data(), in, val)) == VBC_OK)
+            st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, &rec);
+        arena[pass] = std::move(P.ar.host);
+    }
+    if (st != VBC_OK) return st;
+    tv = std::vector<char>();
+    if (arena[0].size() != arena_used)
+        return fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
+    return value_map_host((int)esz, nval, arena[1], arena[0], rec.canon, rec.narrow, map, chunks);
+}
+
 template <typename F>
 static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags, unsigned narrow, F &&build)
 {
-    const bool updatable = (flags & VBC_CREATE_UPDATABLE) != 0;
+    // VBC_CREATE_NARROW_UPDATABLE arrives in `narrow` (check_narrow): the same map, with narrow chunks
+    const bool narrow_updatable = (narrow & VBC_CREATE_NARROW_UPDATABLE) != 0;
+    const bool updatable = (flags & VBC_CREATE_UPDATABLE) != 0 || narrow_updatable;
     flags &= ~VBC_CREATE_UPDATABLE;
     if (updatable && !out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
     if (updatable) *out = nullptr;
@@ -3147,9 +3212,11 @@ static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags
     }
     const LayoutConfig cfg = make_config(dtype, flags, narrow, facts);
     vbc_handle *h = nullptr;
+    bool ft_narrow = false;
     {
         Plan P;
         if (int st = plan_layout(cfg, in.s, v, nval, flags, P, nullptr)) return st;
+        ft_narrow = P.st.ft_narrow;
         if (int st = instantiate(P, cfg, device, &h)) return st;
     }
     h->m = in.s.m;
@@ -3165,32 +3232,15 @@ static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags
         *out = h;
         return VBC_OK;
     }
-    const size_t esz = (size_t)h->esz;
-    int st = VBC_OK;
-    if (nval > kUpdMaxSource) st = fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
-    std::vector<char> arena[2];
-    Recorder rec;
-    std::vector<char> tv((size_t)std::max<int64_t>(nval, 1) * esz, 0);
-    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
-        if (pass == 1)
-            for (int64_t i = 0; i < nval; i++) {
-                const uint64_t tag = (uint64_t)i + 1;
-                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
-            }
-        rec = Recorder{};
-        Plan P;
-        if ((st = build(tv.data(), in, val)) == VBC_OK)
-            st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, &rec);
-        arena[pass] = std::move(P.ar.host);
-    }
-    tv = std::vector<char>();
-    if (st == VBC_OK && arena[0].size() != h->arena_used)
-        st = fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
+    std::vector<uint32_t> map;
+    std::vector<UpdChunk> chunks;
+    int st = plan_value_map(cfg, flags, in, build, ft_narrow, h->arena_used, map, chunks);
     if (st == VBC_OK) {
         DeviceGuard g(h->device);
-        st = g.ok ? build_value_map(h, arena[1], arena[0], rec.canon) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
+        st = g.ok ? upload_value_map(h, map, chunks) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
     }
     if (st != VBC_OK) { release(h); return st; }
+    h->umap.mixed = narrow_updatable;
     h->updatable = true;
     *out = h;
     return VBC_OK;
@@ -3234,6 +3284,9 @@ constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PL
 constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR with it) needs Float32 values "
                                      "on a Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
                                      "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
+constexpr const char *kNarrowUpdPlain = "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES, "
+                                        "which needs Float32 values on a Float64 handle: pass both to vbc1d_create_ex / "
+                                        "vbc2d_create_ex / vbc_csc_create_ex";
 
 static int refuse_sharded_flag(vbc_handle **out)
 {
@@ -3292,6 +3345,7 @@ static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t 
                      int64_t nval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
         sv = v ? v : val;
@@ -3378,6 +3432,7 @@ static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t 
                      int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
         sv = v ? v : val;
@@ -3482,6 +3537,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
                       const void *nzval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     std::vector<char> bv;
     // (the tags of an updatable create go into an nzval-shaped array, before the column blocking copies them)
@@ -3508,6 +3564,9 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
         return st;
     if (flags & (VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS))
         return fail(VBC_INVALID_ARG, "vbcx_plan_image plans one layout: VBC_CREATE_UPDATABLE(_SHARDS) do not change it");
+    if ((flags & VBC_CREATE_NARROW_UPDATABLE) && !(flags & VBC_CREATE_NARROW_VALUES))
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
+    flags &= ~VBC_CREATE_NARROW_UPDATABLE;  // (it changes no layout)
     const unsigned narrow = flags & kNarrowBits;
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
@@ -3521,6 +3580,50 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
     if (!image) return VBC_OK;
     if (capacity < *bytes) return fail(VBC_INVALID_ARG, "image buffer smaller than the arena image");
     std::memcpy(image, P.ar.host.data(), *bytes);
+    return VBC_OK;
+}
+
+static_assert(sizeof(vbcx_map_chunk) == sizeof(UpdChunk) && offsetof(vbcx_map_chunk, vsz) == offsetof(UpdChunk, vsz) &&
+                  offsetof(vbcx_map_chunk, map) == offsetof(UpdChunk, map) && offsetof(vbcx_map_chunk, n) == offsetof(UpdChunk, n),
+              "vbc_host.h vbcx_map_chunk is vbc_handle.h UpdChunk");
+static_assert(VBCX_MAP_ZERO == kUpdZero && VBCX_MAP_SKIP == kUpdSkip && VBCX_MAP_CANON == kUpdCanon, "vbc_host.h map entries");
+
+int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
+                   const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
+                   int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts, uint32_t *map, int64_t map_capacity,
+                   int64_t *nentries, vbcx_map_chunk *chunks, int64_t chunk_capacity, int64_t *nchunks)
+{
+    if (!facts || !nentries || !nchunks) return fail(VBC_INVALID_ARG, "facts, nentries and nchunks must not be NULL");
+    auto stripes = [&](const void *v, StripesInput &in, const void *&sv) {
+        sv = v ? v : val;
+        return pspl ? stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, sv, nval, in)
+                    : stripes_1d(m, n, W, L, spl, pos, idx, ofs, sv, nval, in);
+    };
+    StripesInput in;
+    const void *sv = nullptr;
+    if (int st = stripes(nullptr, in, sv)) return st;
+    flags &= ~(VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS | VBC_CREATE_NARROW_UPDATABLE);
+    const unsigned narrow = flags & kNarrowBits;
+    if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
+    if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
+    flags &= ~kNarrowBits;
+    const LayoutConfig cfg = make_config(dtype, flags, narrow, *facts);
+    size_t arena_used = 0;
+    bool ft_narrow = false;
+    {
+        Plan P;
+        if (int st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, nullptr)) return st;
+        arena_used = P.ar.host.size();
+        ft_narrow = P.st.ft_narrow;
+    }
+    std::vector<uint32_t> mp;
+    std::vector<UpdChunk> ch;
+    if (int st = plan_value_map(cfg, flags, in, stripes, ft_narrow, arena_used, mp, ch)) return st;
+    *nentries = (int64_t)mp.size();
+    *nchunks = (int64_t)ch.size();
+    if (map && map_capacity >= *nentries && !mp.empty()) std::memcpy(map, mp.data(), mp.size() * 4);
+    if (chunks && chunk_capacity >= *nchunks && !ch.empty()) std::memcpy(chunks, ch.data(), ch.size() * sizeof(UpdChunk));
     return VBC_OK;
 }
 
@@ -3849,16 +3952,24 @@ static int convert_values(const void *val, int64_t nval, const vbc_types *t, std
 static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, unsigned &narrow)
 {
     narrow = 0;
-    if (!(flags & kNarrowBits)) return VBC_OK;
+    const bool upd = (flags & VBC_CREATE_NARROW_UPDATABLE) != 0;  // (its refusals name it)
+    if (!(flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE))) return VBC_OK;
+    if (upd && !(flags & VBC_CREATE_NARROW_VALUES))
+        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
     if (!(flags & VBC_CREATE_NARROW_VALUES))
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
-        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES needs val_dtype VBC_F32 and compute_dtype VBC_F64");
+        return refuse_narrow_flag(out, upd ? "VBC_CREATE_NARROW_UPDATABLE with VBC_CREATE_NARROW_VALUES needs val_dtype "
+                                             "VBC_F32 and compute_dtype VBC_F64"
+                                           : "VBC_CREATE_NARROW_VALUES needs val_dtype VBC_F32 and compute_dtype VBC_F64");
     if (flags & VBC_CREATE_UPDATABLE)
-        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_VALUES cannot be combined with VBC_CREATE_UPDATABLE (the update "
-                                       "kernel writes values of the compute eltype)");
-    narrow = flags & kNarrowBits;
-    flags &= ~kNarrowBits;
+        return refuse_narrow_flag(out, upd ? "VBC_CREATE_NARROW_UPDATABLE cannot be combined with VBC_CREATE_UPDATABLE: "
+                                             "pass VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_UPDATABLE alone"
+                                           : "VBC_CREATE_NARROW_VALUES cannot be combined with VBC_CREATE_UPDATABLE (the update "
+                                             "kernel writes values of the compute eltype; a narrow handle is made "
+                                             "updatable by VBC_CREATE_NARROW_UPDATABLE instead)");
+    narrow = flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE);
+    flags &= ~(kNarrowBits | VBC_CREATE_NARROW_UPDATABLE);
     return VBC_OK;
 }
 
@@ -4035,6 +4146,9 @@ int vbc_update_values(vbc_handle *h, const void *val, int64_t nval, int val_dtyp
     if (!h) return fail(VBC_INVALID_ARG, "NULL handle");
     if (!h->updatable) return fail(VBC_INVALID_ARG, "handle created without VBC_CREATE_UPDATABLE");
     if (!known_dtype(val_dtype)) return fail(VBC_UNSUPPORTED_DTYPE, "unknown val_dtype");
+    if (h->umap.mixed && val_dtype != VBC_F32)  // a Float64 val would be rounded in the narrow buckets only
+        return fail(VBC_UNSUPPORTED_DTYPE, "a handle created with VBC_CREATE_NARROW_UPDATABLE takes val_dtype VBC_F32 only "
+                                           "(its narrow buckets store Float32, its wide ones the same values widened)");
     if (h->dtype == VBC_I64 && is_float(val_dtype))
         return fail(VBC_UNSUPPORTED_DTYPE, "floating-point values on an integer handle (InexactError)");
     if (nval < h->nval) return fail(VBC_DIM_MISMATCH, "DimensionMismatch: val shorter than at create");

@@ -103,11 +103,14 @@ struct Stripes {
 // for a word that is no value slot (alignment of a region to 16 bytes; never written).  The entries are cut
 // into chunks of at most kUpdChunkQuads 16-byte quads: `dst` and `map` are element offsets (multiples of a
 // quad) into the arena and the map, 64 bits wide, so only the source index is limited to 32 bits.
+// VBC_CREATE_NARROW_UPDATABLE: a chunk inside a value region stored as Float32 on a Float64 handle has vsz = 4 --
+// its quads are four floats with four entries and `dst` counts floats; every other chunk has vsz = 0 (the
+// compute eltype).  A handle may mix both (vbc_host.h vbcx_map_chunk is this struct).
 struct UpdChunk {
     uint64_t dst;
     uint64_t map;
     uint32_t n;  // quads
-    uint32_t pad;
+    uint32_t vsz;
 };
 constexpr uint32_t kUpdZero = 0xFFFFFFFFu, kUpdSkip = 0xFFFFFFFEu, kUpdCanon = 0x80000000u;
 constexpr int64_t kUpdMaxSource = 0x7FFFFFFE;  // largest nval an updatable handle takes (entries keep bit 31 free)
@@ -118,6 +121,7 @@ struct ValueMap {
     const uint32_t *d_map = nullptr;
     const UpdChunk *d_chunks = nullptr;
     int64_t nchunks = 0, entries = 0;
+    bool mixed = false;  // VBC_CREATE_NARROW_UPDATABLE: chunks say their stored size, Float32 sources only
 };
 
 }  // namespace vbc
@@ -184,8 +188,11 @@ int mul_int(const vbc_handle *h, int trans, const void *x, void *y, double alpha
 int convert_gather(const void *src, int src_dtype, int64_t inc, void *dst, int dst_dtype, int64_t n, hipStream_t s);
 int convert_scatter(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t inc, int64_t n, hipStream_t s);
 // vbc_update.hip
-int build_value_map(vbc_handle *h, const std::vector<char> &tagged, const std::vector<char> &zeroed,
-                    const std::vector<std::pair<size_t, size_t>> &canon);
+typedef std::vector<std::pair<size_t, size_t>> ByteRanges;  // ascending, disjoint byte ranges of an arena image
+int value_map_host(int esz, int64_t nval, const std::vector<char> &tagged, const std::vector<char> &zeroed,
+                   const ByteRanges &canon, const ByteRanges &narrow, std::vector<uint32_t> &map,
+                   std::vector<UpdChunk> &chunks);
+int upload_value_map(vbc_handle *h, const std::vector<uint32_t> &map, const std::vector<UpdChunk> &chunks);
 int update_launch(const vbc_handle *h, const void *d_val, int val_dtype, hipStream_t s);
 // vbc_panel_launch.hip
 int mulmat_panel_any(const vbc_handle *h, int trans, int64_t nrhs, const char *X, int64_t sxr, int64_t sxc, char *Y,

@@ -80,7 +80,12 @@ class _DeviceMatrix:
         the device when the product computes in Float64 (vbc.h VBC_CREATE_NARROW_VALUES: slotted buckets
         only, products bit-identical); for any other eltype pair the attribute is ignored.
         `B.narrow = "planar"` also keeps them narrow in the planar buckets of the plain planar kernels
-        (vbc.h VBC_CREATE_NARROW_PLANAR, passed together with 0x80); any other value raises ValueError."""
+        (vbc.h VBC_CREATE_NARROW_PLANAR, passed together with 0x80); any other value raises ValueError.
+        `B.updatable` is False, True (vbc.h VBC_CREATE_UPDATABLE) or "narrow": updatable, and where narrow
+        storage is in effect (`B.narrow` set, a float32 matrix, Float64 compute) the handle is created with
+        VBC_CREATE_NARROW_UPDATABLE instead of 0x20 and update_values takes float32 values only; where `B.narrow`
+        is unset or ignored, "narrow" behaves as True.  `B.updatable = True` together with `B.narrow` raises
+        ArgumentError; any other value raises ValueError."""
         if multi:  # matrix-core panels: of B for B'X, of Bᵀ for B·X
             flags = _L.VBC_CREATE_MULTI if trans else _L.VBC_CREATE_MULTI_FORWARD
         else:
@@ -92,19 +97,25 @@ class _DeviceMatrix:
             flags = _L.VBC_CREATE_TRANSPOSED if trans else _L.VBC_CREATE_FORWARD
         if getattr(self, "serial", False) and not multi:
             flags |= _L.VBC_CREATE_SERIAL  # the reference's serial per-stripe order in every layout
-        if getattr(self, "updatable", False):
+        updatable = getattr(self, "updatable", False)
+        if not (updatable is False or updatable is None or updatable is True
+                or (isinstance(updatable, str) and updatable == "narrow")):
+            raise ValueError("B.updatable must be False, True or 'narrow', not %r" % (updatable,))
+        if updatable:
             flags |= _L.VBC_CREATE_UPDATABLE  # update_values rewrites the stored values in place
         narrow = getattr(self, "narrow", False)
         if not (narrow is False or narrow is None or narrow is True or (isinstance(narrow, str) and narrow == "planar")):
             raise ValueError("B.narrow must be False, True or 'planar', not %r" % (narrow,))
         if narrow:
-            if getattr(self, "updatable", False):
-                raise _L.ArgumentError("B.narrow and B.updatable cannot be combined (the update kernel writes "
-                                       "values of the compute eltype)")
+            if updatable is True:
+                raise _L.ArgumentError("B.narrow and B.updatable = True cannot be combined (that update writes values "
+                                       "of the compute eltype): set B.updatable = 'narrow'")
             if not multi and self._val.dtype == np.float32 and compute == _L.VBC_F64:
                 flags |= _L.VBC_CREATE_NARROW_VALUES  # Float32 values in HBM, widened in registers
                 if narrow == "planar":
                     flags |= _L.VBC_CREATE_NARROW_PLANAR  # the plain planar buckets too
+                if updatable:  # "narrow": the narrow handle plus a value map; its updates take float32 values only
+                    flags = (flags & ~_L.VBC_CREATE_UPDATABLE) | _L.VBC_CREATE_NARROW_UPDATABLE
         return self._handles.get((int(device), flags, compute),
                                  lambda out: self._create(out, int(device), flags, compute))
 
@@ -170,6 +181,9 @@ class _DeviceMatrix:
         code = _L.dtype_code(val.dtype)
         if self._val.dtype.kind != "f" and code in (_L.VBC_F64, _L.VBC_F32):
             raise _L.UnsupportedDtype("floating-point values for an integer matrix (InexactError)")
+        if code != _L.VBC_F32 and any(flags & _L.VBC_CREATE_NARROW_UPDATABLE for _, flags, _ in self._handles.h):
+            raise _L.UnsupportedDtype("a handle of this matrix stores Float32 values (B.updatable = 'narrow'): "
+                                      "update_values takes float32 values only")  # before any handle is touched
         is_torch = type(val).__module__.startswith("torch")
         host = None
         if is_torch:

@@ -19,6 +19,14 @@ devices = [0] * N: every shard on one GPU, no communicator), with the same proto
        val -- and the pack kernel alone as the difference of the two graph times;
   (c) destroy + create of the sharded handle with new values, not updatable (wall clock);
   (d) create with and without VBC_CREATE_UPDATABLE_SHARDS; (e) one B'x product.
+
+--narrow [--processes 3] measures the update of a narrow handle (vbc.h VBC_CREATE_NARROW_UPDATABLE): the bench's
+FE-2D matrix as float32 on Float64 B'x handles, a device val of float32, in `--processes` fresh processes that each
+time both handles alternately (events around a graph of K updates, median of 5, twice each):
+  (a) the wide updatable handle (VBC_CREATE_UPDATABLE, float32 val widened by the kernel);
+  (b) the VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_UPDATABLE handle;
+and one B'x product of (b) against the narrow handle that is not updatable (the same kernel on the same bytes).
+(b) counts as faster only if the gap of the medians exceeds (a)'s own process-to-process range.
 """
 import argparse
 import json
@@ -155,8 +163,92 @@ def sharded_main(args, torch, V, B):
     return 0 if out["update_below_recreate"] and out["bitwise_equal_to_recreated"] else 1
 
 
+def narrow_child(args, torch, V):
+    """One fresh process of --narrow: both updatable handles timed alternately, then the two narrow products."""
+    import bench
+    L, lib = V._lib, V._lib.lib()
+    B = bench.build_matrix("fe", np.float32, args.scale)
+    rng = np.random.default_rng(7)
+    v2 = rng.uniform(-1, 1, len(B.val)).astype(np.float32)
+    d2 = torch.from_numpy(v2).cuda()
+
+    def make(narrow, updatable, val=None):
+        M = V.SparseMatrix1DVBC(B.W, B.m, B.n, B.Phi, B.pos, B.idx, B.ofs, B.val if val is None else val)
+        M.narrow, M.updatable = narrow, updatable
+        return M, M.handle(0, True, compute=L.VBC_F64)
+    (A, ha), (Nu, hb), (Nn, _) = make(False, True), make(True, "narrow"), make(True, False, v2)
+    ia, ib, inn = (M.info(trans=True, compute=L.VBC_F64) for M in (A, Nu, Nn))
+    assert ib["narrow_t"] and not ia["narrow_t"]
+    s = torch.cuda.Stream()
+
+    def update(h):
+        return lambda: L.check(lib.vbc_update_values(h, d2.data_ptr(), len(v2), L.VBC_F32, L.VBC_MEM_DEVICE, s.cuda_stream))
+    ta, tb = [], []
+    for _ in range(2):  # alternately
+        ta += graph_time_us(torch, s, update(ha), args.steps, args.warmup)[1]
+        tb += graph_time_us(torch, s, update(hb), args.steps, args.warmup)[1]
+    x = torch.from_numpy(rng.uniform(-1, 1, B.m)).cuda()
+    y, y2 = (torch.empty(B.n, dtype=torch.float64, device="cuda") for _ in range(2))
+    pu, pn = [], []
+    for _ in range(2):
+        pu += graph_time_us(torch, s, lambda: V.mul_(y, Nu.T, x), args.steps, args.warmup)[1]
+        pn += graph_time_us(torch, s, lambda: V.mul_(y2, Nn.T, x), args.steps, args.warmup)[1]
+    torch.cuda.synchronize()
+    slots_b = (ib["device_bytes"] - inn["device_bytes"]) // 4  # the map's size (and the chunk table)
+    print(json.dumps({"wide_updatable_us": round(float(np.median(ta)), 2), "wide_updatable_us_all": ta,
+                      "narrow_updatable_us": round(float(np.median(tb)), 2), "narrow_updatable_us_all": tb,
+                      "product_narrow_updatable_us": round(float(np.median(pu)), 2), "product_narrow_updatable_us_all": pu,
+                      "product_narrow_us": round(float(np.median(pn)), 2), "product_narrow_us_all": pn,
+                      "bitwise_equal_to_created": bool(torch.equal(y, y2)),
+                      "m": B.m, "n": B.n, "nval": int(B.ofs[-1]) - 1, "value_slots_narrow": int(slots_b),
+                      "device_bytes": {"wide_updatable": ia["device_bytes"], "narrow_updatable": ib["device_bytes"],
+                                       "narrow": inn["device_bytes"]}}))
+    return 0
+
+
+def narrow_main(args):
+    """--narrow: `--processes` fresh processes, one after the other, each timing both handles; this process only
+    starts them and gathers their lines (it never opens the GPU)."""
+    import subprocess
+    runs = []
+    for _ in range(args.processes):
+        r = subprocess.run([sys.executable, __file__, "--narrow", "--child", "--scale", str(args.scale), "--steps",
+                            str(args.steps), "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-2000:])
+            return 1
+        runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+
+    def summary(key):
+        v = [p[key] for p in runs]
+        return {"per_process_median_us": v, "median_us": round(float(np.median(v)), 2), "min_us": min(v), "max_us": max(v)}
+    a, b = summary("wide_updatable_us"), summary("narrow_updatable_us")
+    pu, pn = summary("product_narrow_updatable_us"), summary("product_narrow_us")
+    gap = a["median_us"] - b["median_us"]
+    out = {"tool": "update_time", "mode": "narrow", "workload": "fe", "scale": args.scale, "values": "float32",
+           "compute": "float64", "product": "B'x", "processes": args.processes, "steps": args.steps, "warmup": args.warmup,
+           "update_wide_updatable_0x20": a, "update_narrow_updatable_0x80_0x200": b, "gap_us": round(gap, 2),
+           "wide_process_range_us": round(a["max_us"] - a["min_us"], 2),
+           # (b) counts as faster only if the gap exceeds (a)'s own process-to-process range
+           "narrow_update_faster": bool(gap > a["max_us"] - a["min_us"]),
+           "bytes_per_slot_model": {"wide": 16, "narrow": 12},
+           "product_narrow_updatable": pu, "product_narrow_not_updatable": pn,
+           "product_ranges_overlap": bool(pu["min_us"] <= pn["max_us"] and pn["min_us"] <= pu["max_us"]),
+           "bitwise_equal_to_created": all(p["bitwise_equal_to_created"] for p in runs), "runs": runs}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    return 0 if out["bitwise_equal_to_created"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--narrow", action="store_true",
+                    help="FE-2D as float32 on Float64 handles: the wide updatable handle against the narrow-updatable one")
+    ap.add_argument("--processes", type=int, default=3, help="--narrow: fresh processes, each timing both handles")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--workload", default="fe", choices=["fe", "ldoor"])
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--steps", type=int, default=20)
@@ -165,10 +257,15 @@ def main():
     ap.add_argument("--shards", type=int, default=0, help="N > 0: the sharded handle on devices = [0] * N")
     ap.add_argument("--split", default="stripes", choices=["stripes", "rows"])
     args = ap.parse_args()
+    if args.narrow and not args.child:
+        return narrow_main(args)
     import torch
 
     import bench
     import sparsematrixvbcs_amd as V
+
+    if args.narrow:
+        return narrow_child(args, torch, V)
 
     B = bench.build_matrix(args.workload, np.float64, args.scale)
     if args.shards > 0:
