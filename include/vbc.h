@@ -28,7 +28,7 @@
  * vbc_sharded_update_values (vbc_info unchanged by both).  VBC_CREATE_NARROW_VALUES came without a version
  * bump (vbc_version() still returns 30400, no new symbol): a binding detects the capability by a create with
  * the flag succeeding and by vbc_info.planar_mask bits 12 / 13; a library without it refuses nothing and
- * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15. */
+ * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15; VBC_CREATE_NARROW_PAIRS: bits 16 / 17. */
 #define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
@@ -176,6 +176,30 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       binding detects the capability by the create succeeding and a following
                                       vbc_update_values returning VBC_OK; a library without it ignores the bit and
                                       its vbc_update_values returns VBC_INVALID_ARG. */
+
+#define VBC_CREATE_NARROW_PAIRS 0x400u /* Only together with VBC_CREATE_NARROW_VALUES and VBC_CREATE_NARROW_PLANAR (so
+                                      on the *_ex creates with Float32 values on a Float64 handle): the handle does
+                                      everything 0x180 does and also keeps Float32 values in every bucket the
+                                      lane-pair kernels run -- spmv_planar_pair, the B'x form and the forward form of
+                                      3 x 3 node blocks (planar_mask bit 11), whatever its variant (affine staged or
+                                      direct y writes, table-mapped outputs, masked order, 32-bit or int16 keys), and
+                                      spmv_pair_lanes (lane-pair streams), in whichever direction's layout it sits.
+                                      A narrow run-row holds the wide one's 288 values as 288 floats (1152 B, 16-B
+                                      aligned, no padding), rows in the same order; a lane widens each value as the
+                                      operand of the multiply-add that folds it.  As with 0x80 / 0x100 no layout decision
+                                      changes and every product is bit-identical to that of the handle created with
+                                      0x180 (and so to the wide handle's).  Buckets of spmv_planar_lanes, the split
+                                      and fused-split kernels keep Float64 values; so do the swept, merge and panel /
+                                      tile layouts.  vbc_info.planar_mask bit 16 / 17 say whether a B'x / forward
+                                      lane-pair bucket stores Float32 (bits 14 / 15 keep meaning the plain planar
+                                      buckets); bytes_t, bytes_f and device_bytes count the bytes really stored.
+                                      May be combined with VBC_CREATE_NARROW_UPDATABLE.  Refused (VBC_INVALID_ARG, no
+                                      device work, no handle): 0x400 without 0x80 or without 0x100, 0x400 together
+                                      with VBC_CREATE_UPDATABLE (0x20), and every create that refuses 0x80 (the
+                                      creates without vbc_types, any other eltype pair, both sharded creates with or
+                                      without VBC_CREATE_UPDATABLE_SHARDS).  No version bump and no new symbol, as
+                                      with 0x80 / 0x100: a binding detects the capability by bits 16 / 17; a library
+                                      without it ignores the bit. */
 
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
@@ -461,7 +485,9 @@ typedef struct vbc_info {
                                B'x slotted bucket stores Float32 values on this Float64 handle
                                (VBC_CREATE_NARROW_VALUES), bit 13: some forward bucket does; bit 14: some B'x
                                planar bucket (spmv_planar) stores Float32 values (VBC_CREATE_NARROW_PLANAR),
-                               bit 15: some forward planar bucket (spmv_planar_fwd) does */
+                               bit 15: some forward planar bucket (spmv_planar_fwd) does; bit 16: some B'x
+                               lane-pair bucket (spmv_planar_pair, spmv_pair_lanes) stores Float32 values
+                               (VBC_CREATE_NARROW_PAIRS), bit 17: some forward lane-pair bucket does */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

@@ -20,6 +20,8 @@ struct LayoutConfig {
     bool narrow_values = false;   // VBC_CREATE_NARROW_VALUES (fp64 handle of Float32 values): slotted bins store floats
     bool narrow_planar = false;   // VBC_CREATE_NARROW_PLANAR (only with narrow_values): so do the chunk-planar bins of
                                   // spmv_planar / spmv_planar_fwd (not pair, lanes or split)
+    bool narrow_pairs = false;    // VBC_CREATE_NARROW_PAIRS (only with narrow_planar): so do the lane-pair bins of
+                                  // spmv_planar_pair / spmv_pair_lanes (288 floats per run-row)
     int target_ranges_m = 4096;
     int panel_valu = 0;           // ablation bits of the panel kernel (VBC_PANEL_VALU / VBC_PANEL_DIAG, the VBC_ABLATION
                                   // build only; 0 in the product library)
@@ -115,7 +117,7 @@ struct LayoutConfig {
 
 // The whole environment block of a create.  `flags`: vbc_create_flags (VBC_CREATE_SERIAL overrides two knobs, the
 // MULTI flags enable the panel / tile knobs).  `narrow`: the narrow-storage bits the create accepted
-// (VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR; 0: none) -- they are not part of `flags`.
+// (VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR, VBC_CREATE_NARROW_PAIRS; 0: none) -- they are not part of `flags`.
 LayoutConfig make_config(int dtype, unsigned flags, unsigned narrow, const DeviceFacts &facts);
 
 }  // namespace vbc

@@ -478,6 +478,38 @@ static int slot_runs(const PlanCtx *h, const std::vector<Entry> &ents, const std
 // chunks balanced by rows.  ents[sbeg[q] ...] are segment q's entries (keys = gather index only).
 // pair_only: build nothing and return kBuildDeclined unless the bucket takes the lane-pair layout.
 constexpr int kBuildDeclined = -1;
+
+// One run's 3 x 3 values v[row][column] at stripe (stream) slot sl of the pair run-row at `blk` (vbc_planar.h
+// run_pair: segments A, B, C, D of 288 values).  narrow (VBC_CREATE_NARROW_PAIRS): the run-row holds floats, in the
+// arrangement VBC_PAIR_FORM names (vbc_kernels.h; vbc_planar.h pair_load reads it).
+static void put_pair_run(const PlanCtx *h, bool narrow, char *blk, int sl, const double (&v)[3][3])
+{
+    auto put = [&](int e, const double &src) {
+        if (narrow) narrow_value(h, &src, blk + (size_t)e * 4);
+        else std::memcpy(blk + (size_t)e * 8, &src, 8);
+    };
+    if (narrow && VBC_PAIR_FORM == 1) {  // 16 B per lane: even {r0c0, r0c1, r1c0, r1c1}, odd {r0c2, r1c2, r2c2, r2c0}; r2c1 tail
+        put(8 * sl + 0, v[0][0]);
+        put(8 * sl + 1, v[0][1]);
+        put(8 * sl + 2, v[1][0]);
+        put(8 * sl + 3, v[1][1]);
+        put(8 * sl + 4, v[0][2]);
+        put(8 * sl + 5, v[1][2]);
+        put(8 * sl + 6, v[2][2]);
+        put(8 * sl + 7, v[2][0]);
+        put(256 + sl, v[2][1]);
+        return;
+    }
+    put(4 * sl + 0, v[0][0]);
+    put(4 * sl + 1, v[0][1]);
+    put(4 * sl + 2, v[0][2]);
+    put(4 * sl + 3, v[1][2]);
+    put(128 + 2 * sl + 0, v[1][0]);
+    put(128 + 2 * sl + 1, v[1][1]);
+    put(192 + sl, v[2][2]);
+    put(224 + 2 * sl + 0, v[2][0]);
+    put(224 + 2 * sl + 1, v[2][1]);
+}
 static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<Entry> &ents,
                        const std::vector<int64_t> &sbeg0, const std::vector<int32_t> &out0, int64_t total_entries,
                        const char *val, Arena &ar, int &range0, PendingSlot &ps,
@@ -666,12 +698,15 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
     // VBC_CREATE_NARROW_PLANAR: so does a chunk-planar bin the plain kernel runs (spmv_planar: not pair, not split
     // -- which covers the fused small-matrix launch and runs with holes; lane streams are build_lanes'), its
     // chunk rows in the Float32 column-group arrangement (planar_off(4, ...), rows of 64 * w floats: 16-B aligned)
-    const bool narrow = esz == 8 && (planar ? h->narrow_planar && !pair && split == 1 && !b.fused && !holes
-                                            : h->narrow_values);
+    // VBC_CREATE_NARROW_PAIRS: so does a lane-pair bin (spmv_planar_pair, B'x or the forward DOT form: never split,
+    // fused or with holes), its run-rows the wide ones' 288 values as floats in put_pair_run's arrangement (1152 B: 16-B aligned)
+    const bool narrow = esz == 8 && (pair ? h->narrow_pairs
+                                          : planar ? h->narrow_planar && split == 1 && !b.fused && !holes
+                                                   : h->narrow_values);
     const int vsz = narrow ? 4 : esz;
     b.vsz = narrow ? 4 : 0;
     ps.o_val = ar.reserve(E * w * vsz * (pair ? 3 : 1));
-    if (narrow && h->rec) h->rec->narrow.emplace_back(ps.o_val, ps.o_val + (size_t)E * w * vsz);
+    if (narrow && h->rec) h->rec->narrow.emplace_back(ps.o_val, ps.o_val + (size_t)E * w * vsz * (pair ? 3 : 1));
     ps.o_out = ar.reserve(std::max<size_t>(out.size(), 1) * 4);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
     ps.o_rchunk = ar.reserve(rchunk.size() * 4);
@@ -683,11 +718,10 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
     char *vv = ar.at<char>(ps.o_val);
     int64_t row = 0;
     if (pair) {  // run-rows of 32 stripes: segments A (64 lanes x 16 B), B, C, D (vbc_planar.h run_pair)
-        double *dv = reinterpret_cast<double *>(vv);
         for (int64_t c = 0; c < nch; c++) {
             for (int32_t qr = 0; qr < cr[c]; qr++, row++) {
                 const uint32_t last = qr + 1 == cr[c] ? kLast : 0u;
-                double *blk = dv + row * 288;
+                char *blk = vv + row * 288 * vsz;
                 if (b.mask) {  // live stripe slots of this run-row: a prefix in chunk-local length order
                     uint32_t nl = 0;
                     for (int sl = 0; sl < 32; sl++) {
@@ -710,15 +744,7 @@ static int build_slots(PlanCtx *h, int kind, int w, int wsrc, const std::vector<
                     } else {
                         key[e] = kPad | last;
                     }
-                    blk[4 * sl + 0] = v[0][0];
-                    blk[4 * sl + 1] = v[0][1];
-                    blk[4 * sl + 2] = v[0][2];
-                    blk[4 * sl + 3] = v[1][2];
-                    blk[128 + 2 * sl + 0] = v[1][0];
-                    blk[128 + 2 * sl + 1] = v[1][1];
-                    blk[192 + sl] = v[2][2];
-                    blk[224 + 2 * sl + 0] = v[2][0];
-                    blk[224 + 2 * sl + 1] = v[2][1];
+                    put_pair_run(h, narrow, blk, sl, v);
                 }
             }
         }
@@ -927,7 +953,13 @@ static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const 
     ps.real = real;
     const int64_t vals_per_row = pair ? 288 : (int64_t)64 * w;
     const int64_t keys_per_row = NS;
-    ps.o_val = ar.reserve((size_t)rows * vals_per_row * esz);
+    // VBC_CREATE_NARROW_PAIRS (build_slots): the lane-pair streams store floats, run-rows of 288 (put_pair_run);
+    // everything above was decided with esz.  Plain lane streams stay wide.
+    const bool narrow = pair && h->narrow_pairs;
+    const int vsz = narrow ? 4 : esz;
+    b.vsz = narrow ? 4 : 0;
+    ps.o_val = ar.reserve((size_t)rows * vals_per_row * vsz);
+    if (narrow && h->rec) h->rec->narrow.emplace_back(ps.o_val, ps.o_val + (size_t)rows * vals_per_row * vsz);
     ps.o_out = ar.reserve(4);
     ps.o_rrow = ar.reserve(rrow.size() * 4);
     ps.o_rchunk = ar.reserve(rchunk.size() * 4);
@@ -947,7 +979,7 @@ static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const 
     uint32_t *key = ar.at<uint32_t>(ps.o_key);
     uint32_t *nlv = ar.at<uint32_t>(ps.o_nlive);
     char *vv = ar.at<char>(ps.o_val);
-    std::memset(vv, 0, (size_t)rows * vals_per_row * esz);
+    std::memset(vv, 0, (size_t)rows * vals_per_row * vsz);
     std::memset(key, 0, (size_t)rows * keys_per_row * 4);
     for (int64_t t = 0; t < ntiles; t++) {
         const int64_t R0 = trow[t], T = (trow[t + 1] - R0) / rows_per_step;
@@ -972,16 +1004,7 @@ static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const 
                         double v[3][3];
                         for (int d = 0; d < 3; d++)
                             std::memcpy(v[d], val + ents[sbeg[q] + u * 3 + d].voff * esz, 3 * sizeof(double));
-                        double *blk = reinterpret_cast<double *>(vv) + row0 * 288;
-                        blk[4 * l + 0] = v[0][0];
-                        blk[4 * l + 1] = v[0][1];
-                        blk[4 * l + 2] = v[0][2];
-                        blk[4 * l + 3] = v[1][2];
-                        blk[128 + 2 * l + 0] = v[1][0];
-                        blk[128 + 2 * l + 1] = v[1][1];
-                        blk[192 + l] = v[2][2];
-                        blk[224 + 2 * l + 0] = v[2][0];
-                        blk[224 + 2 * l + 1] = v[2][1];
+                        put_pair_run(h, narrow, vv + row0 * 288 * vsz, l, v);
                         continue;
                     }
                     for (int d = 0; d < run; d++) {
@@ -1620,12 +1643,12 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
     commit_launch_keys(h, pss, ar);
     for (const PendingSlot &ps : pss) {  // slotted bins: padded rows x (index bytes + values)
         if (ps.b.lanes) {  // lanes: real rows' values, one key per run, nlive per row, the tile tables
-            h->st.bytes_t += ps.real * (int64_t)ps.b.w * h->esz + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
+            h->st.bytes_t += ps.real * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
         } else if (ps.b.mask) {  // masked: padding lanes fetch nothing; + the per-row live counts
             const double f = (double)ps.real / (double)std::max<int64_t>(1, ps.rows * ps.b.rpi);
             h->st.bytes_t += ps.real * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + (int64_t)(f * (double)ps.key_bytes) + ps.rows * 4;
-        } else {
-            h->st.bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
+        } else {  // (a pair bin's rows are run-rows: 3 rows of every stripe slot, 288 values)
+            h->st.bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.pair ? 3 : 1) * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
         }
     }
     L.total_ranges = range0;
@@ -2022,7 +2045,7 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                     h->st.bytes_f += p1.real * (int64_t)R * h->esz + p1.key_bytes + p1.rows * 4 +
                                   (int64_t)p1.b.ntiles * (8 + 128) + s.m * h->esz;
                 else if (fpair)  // run-rows of 32 blocks (288 values), one key per block, y
-                    h->st.bytes_f += p1.rows * 288 * (int64_t)h->esz + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
+                    h->st.bytes_f += p1.rows * 288 * (int64_t)(p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
                                   s.m * h->esz;
                 else
                     h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
@@ -3011,6 +3034,7 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
             cfg_c.narrow_values = cfg.narrow_values &&
                                   (rec ? rec->ft_narrow : all_float_exact(cv.data(), (int64_t)(cv.size() / 8)));
             cfg_c.narrow_planar = cfg.narrow_planar && cfg_c.narrow_values;
+            cfg_c.narrow_pairs = cfg.narrow_pairs && cfg_c.narrow_planar;
             h->st.ft_narrow = cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
             st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
@@ -3280,8 +3304,10 @@ static int refuse_narrow_flag(vbc_handle **out, const char *why)
     if (out) *out = nullptr;
     return fail(VBC_INVALID_ARG, why);
 }
-constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR;
-constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR with it) needs Float32 values "
+constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS;
+constexpr const char *kNarrowPairsAlone = "VBC_CREATE_NARROW_PAIRS is valid only together with VBC_CREATE_NARROW_VALUES and "
+                                          "VBC_CREATE_NARROW_PLANAR";
+constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR / VBC_CREATE_NARROW_PAIRS with it) needs Float32 values "
                                      "on a Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
                                      "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
 constexpr const char *kNarrowUpdPlain = "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES, "
@@ -3570,6 +3596,7 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
     const unsigned narrow = flags & kNarrowBits;
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
+    if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
     if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
     flags &= ~kNarrowBits;
     Plan P;
@@ -3606,6 +3633,7 @@ int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const 
     const unsigned narrow = flags & kNarrowBits;
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
+    if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
     if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
     flags &= ~kNarrowBits;
     const LayoutConfig cfg = make_config(dtype, flags, narrow, *facts);
@@ -3708,14 +3736,15 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
             if (b.vsz) info->planar_mask |= 1 << 13;
     if (h->has_t)
         for (const SlotBin &b : h->lt.pbins)
-            if (b.vsz) info->planar_mask |= 1 << 14;  // B'x planar buckets of Float32 values (VBC_CREATE_NARROW_PLANAR)
+            if (b.vsz) info->planar_mask |= 1 << (b.pair ? 16 : 14);  // B'x planar buckets of Float32 values (VBC_CREATE_NARROW_
+                                                                      // PLANAR); lane-pair ones (VBC_CREATE_NARROW_PAIRS)
     if (h->has_f)
         for (const auto &l : h->lf)
             for (const SlotBin &b : l.pbins)
-                if (b.vsz) info->planar_mask |= 1 << 15;  // forward ones
+                if (b.vsz) info->planar_mask |= 1 << (b.pair ? 17 : 15);  // forward ones
     if (h->has_ft)
         for (const SlotBin &b : h->lft.pbins)
-            if (b.vsz) info->planar_mask |= 1 << 15;
+            if (b.vsz) info->planar_mask |= 1 << (b.pair ? 17 : 15);
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3956,6 +3985,9 @@ static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, u
     if (!(flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE))) return VBC_OK;
     if (upd && !(flags & VBC_CREATE_NARROW_VALUES))
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
+    if ((flags & VBC_CREATE_NARROW_PAIRS) && (flags & (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR)) !=
+                                                 (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR))
+        return refuse_narrow_flag(out, kNarrowPairsAlone);
     if (!(flags & VBC_CREATE_NARROW_VALUES))
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)

@@ -25,6 +25,13 @@
 
 #include "vbc_internal.h"  // VBC_ABL
 
+// The arrangement of a narrow lane-pair run-row (VBC_CREATE_NARROW_PAIRS; vbc_planar.h pair_load, vbc_device.hip
+// put_pair_run): 0 = the wide run-row's element offsets, 1 = 16 B per lane and a tail.  A build-time choice so both
+// can be measured (make pair_form_alt builds the other one); DESIGN.md §10.3 says which is kept and why.
+#ifndef VBC_PAIR_FORM
+#define VBC_PAIR_FORM 1
+#endif
+
 namespace vbc {
 
 constexpr int kBlockThreads = 256;
@@ -137,8 +144,9 @@ struct SlotBin {
                            // row's dot product with the x slice is added to its sum (the reference's forward order)
     int32_t vsz;           // slotted: 4 = `val` holds Float32 values on an fp64 handle (VBC_CREATE_NARROW_VALUES:
                            // widened in registers, every bin of the launch alike); 0 = values of the compute eltype.
-                           // Planar (VBC_CREATE_NARROW_PLANAR; spmv_planar / spmv_planar_fwd bins only, never pair,
-                           // lanes or split): 4 = chunk rows in the Float32 column-group arrangement, planar_off(4, ..)
+                           // Planar (VBC_CREATE_NARROW_PLANAR; spmv_planar / spmv_planar_fwd bins only, never plain
+                           // lanes or split): 4 = chunk rows in the Float32 column-group arrangement, planar_off(4, ..).
+                           // Pair (VBC_CREATE_NARROW_PAIRS; spmv_planar_pair / spmv_pair_lanes): 4 = run-rows of 288 floats
 };
 
 // Runs with holes (SlotBin::holes): the run's stored-row mask above the gather index of its first key.

@@ -804,18 +804,85 @@ __global__ __launch_bounds__(64 * P) void spmv_planar_fwd_split(const SlotBin b,
 // product of its output row with the x slice to its accumulator: y[i] += (B[i][j] x[j] + B[i][j+1] x[j+1]) +
 // B[i][j+2] x[j+2], blocks in stripe order -- the association of the reference's serial forward loop
 // (multiply_1DVBC.jl:34, :62-71) and of run_planar_fwd, so the forward product stays bit-identical to it.
-template <int NRS, bool FASTE, int NB, bool KC, bool MASK = false, bool DOT = false>
+// S: the stored value type (default double).  S = float (VBC_CREATE_NARROW_PAIRS): a run-row is the same 288
+// values as floats (1152 B) in one of two arrangements (pair_load below; form 1 is the one kept, DESIGN.md
+// §10.3).  Form 0 keeps the wide element offsets, so a lane's three loads are 8 B each; there the odd lane's single
+// value of segment C sits on a 4-B boundary, and where the issue of this work suggested a lone 4-B load pair_ld1
+// loads the aligned float pair that holds it and keeps that element -- one instruction for the whole wave, inside
+// segment C (192 .. 223; a dead pair's 192 is even); adjacent odd lanes fetch the same 8 B.  The pipeline
+// registers hold floats and each value is widened (exactly) as the operand of the fmadd (DOT: multiply) that
+// consumes it.  Keys, nlive, gathers, the DPP exchange, the fold order and the y writes are those of double.
+template <typename S>
+__device__ __forceinline__ auto pair_ld1(gptr<const S> rowp, int m1, bool odd)
+{
+    typedef S s2 __attribute__((ext_vector_type(2)));
+    if constexpr (sizeof(S) == 8) {
+        return *(const __attribute__((address_space(1))) s2 *)(rowp + m1);  // 8-B aligned (odd lanes)
+    } else {
+        // floats: the even lane's {B[2ps], B[2ps+1]} is 8-B aligned; the odd lane needs C[ps] alone (its .x), at a
+        // 4-B aligned offset -- it loads the aligned float pair that holds it and keeps that element
+        const s2 t = *(gptr<const s2>)(rowp + (odd ? (m1 & ~1) : m1));
+        s2 r = t;
+        r.x = (odd && (m1 & 1)) ? t.y : t.x;
+        return r;
+    }
+}
+
+// The run-row arrangement of floats (vbc_kernels.h VBC_PAIR_FORM, shared with the host writer put_pair_run):
+// form 0 as above; form 1: lane l's 16 B at element 4 l -- even {r0c0, r0c1, r1c0, r1c1}, odd {r0c2, r1c2, r2c2,
+// r2c0} -- and the 32 r2c1 as a 128-B tail at element 256 + ps, so a lane loads 16 B + 4 B and the even lane
+// receives r2c0 over the DPP swap (pair_r2).  Either way v[0], v[1] hold what the wide kernel's do.
+template <typename S>
+using pair_s2 = S __attribute__((ext_vector_type(2)));
+template <typename S>
+constexpr bool pair_form_b = sizeof(S) == 4 && VBC_PAIR_FORM == 1;
+
+// mlane / mps: the lane and pair whose addresses this lane reads (its own; pair 0's for a dead pair)
+template <typename S>
+__device__ __forceinline__ void pair_load(gptr<const S> rowp, int m0, int m1, int m2, bool odd, int mlane, int mps,
+                                          pair_s2<S> (&v)[3])
+{
+    typedef S s2 __attribute__((ext_vector_type(2)));
+    if constexpr (pair_form_b<S>) {
+        typedef S s4 __attribute__((ext_vector_type(4)));
+        const s4 q = __builtin_nontemporal_load((gptr<const s4>)(rowp + 4 * mlane));
+        v[0] = s2{q.x, q.y};
+        v[1] = s2{q.z, q.w};
+        v[2] = s2{__builtin_nontemporal_load(rowp + 256 + mps), S(0)};  // (the odd lane does not use it)
+    } else {
+        v[0] = __builtin_nontemporal_load((gptr<const s2>)(rowp + m0));
+        v[1] = pair_ld1<S>(rowp, m1, odd);
+        v[2] = __builtin_nontemporal_load((gptr<const s2>)(rowp + m2));
+    }
+}
+
+// {r2c0, r2c1} of the even lane (the odd lane's result is unused)
+template <typename S>
+__device__ __forceinline__ auto pair_r2(const pair_s2<S> (&v)[3])
+{
+    typedef S s2 __attribute__((ext_vector_type(2)));
+    if constexpr (pair_form_b<S>) {
+        const S send = v[1].y;  // (a copy: __builtin_bit_cast of the element expression itself read element 0)
+        const int got = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true);  // the odd lane's r2c0
+        return s2{__builtin_bit_cast(S, got), v[2].x};
+    } else {
+        return v[2];
+    }
+}
+
+template <int NRS, bool FASTE, int NB, bool KC, bool MASK = false, bool DOT = false, typename S = double>
 __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, const double *__restrict__ x,
                                          double *__restrict__ y, double alpha, double beta, bool rd, char *lds_wave,
                                          int *lds_out)
 {
     typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef S s2 __attribute__((ext_vector_type(2)));
     const int R0 = G(b.rrow)[r], R1 = G(b.rrow)[r + 1];
     if (R0 >= R1) return;
     int c = G(b.rchunk)[r];
     const bool odd = (lane & 1) != 0;
     const int ps = lane >> 1;  // stripe slot of the pair
-    const gptr<const double> val = G(static_cast<const double *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const double> xg = G(x);
     typedef __attribute__((address_space(4))) const uint32_t *cptr;
@@ -824,15 +891,16 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
     const cptr nlive = (cptr)b.nlive;
     // per-lane element offsets of the three value loads inside a run-row
     const int o0 = 2 * lane, o1 = odd ? 192 + ps : 128 + 2 * ps, o2 = 224 + 2 * ps;
-    auto load = [&](int R, uint32_t (&kk)[NRS], uint32_t (&bs)[NRS], int (&nl)[NRS], d2 (&v)[NRS][3]) {
+    auto load = [&](int R, uint32_t (&kk)[NRS], uint32_t (&bs)[NRS], int (&nl)[NRS], s2 (&v)[NRS][3]) {
 #pragma unroll
         for (int j = 0; j < NRS; j++) {
             const int Rc = min(R + j, R1 - 1);
-            int mps = ps, m0 = o0, m1 = o1, m2 = o2;
+            int mps = ps, m0 = o0, m1 = o1, m2 = o2, mlane = lane;
             if constexpr (MASK) {  // dead pairs: pair 0's addresses (lane parity kept)
                 nl[j] = (int)nlive[Rc];
                 const bool dead = ps >= nl[j];
                 mps = dead ? 0 : ps;
+                mlane = dead ? (odd ? 1 : 0) : lane;
                 m0 = dead ? (odd ? 1 : 0) * 2 : o0;
                 m1 = dead ? (odd ? 192 : 128) : o1;
                 m2 = dead ? 224 : o2;
@@ -844,10 +912,8 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
                 kk[j] = key[(size_t)Rc * 32 + mps];
                 bs[j] = 0;
             }
-            const gptr<const double> rowp = val + (size_t)Rc * 288;
-            v[j][0] = __builtin_nontemporal_load((gptr<const d2>)(rowp + m0));
-            v[j][1] = *(const __attribute__((address_space(1))) d2 *)(rowp + m1);  // 8-B aligned (odd lanes)
-            v[j][2] = __builtin_nontemporal_load((gptr<const d2>)(rowp + m2));
+            const gptr<const S> rowp = val + (size_t)Rc * 288;
+            pair_load<S>(rowp, m0, m1, m2, odd, mlane, mps, v[j]);
         }
     };
     constexpr uint32_t kPad16 = 0xFFFF8000u;
@@ -922,7 +988,7 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
     auto compute = [&](int R, const uint32_t (&kk)[NRS], const uint32_t (&bs)[NRS], const int (&nl)[NRS],
-                       const d2 (&v)[NRS][3], const d2 (&xv)[NRS]) {
+                       const s2 (&v)[NRS][3], const d2 (&xv)[NRS]) {
 #pragma unroll
         for (int j = 0; j < NRS; j++) {
             const bool pad = MASK ? ps >= nl[j] : (KC ? kk[j] == kPad16 : (kk[j] & kPad) != 0);
@@ -935,18 +1001,19 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
             const double other = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
             double x0 = odd ? other : xv[j].x, x1 = odd ? xv[j].x : xv[j].y, x2 = odd ? xv[j].y : other;
             if (pad) x0 = x1 = x2 = 0.0;
+            const s2 r2 = pair_r2<S>(v[j]);
             // even: v[0] = {r0c0, r0c1}, v[1] = {r1c0, r1c1}, v[2] = {r2c0, r2c1}
             // odd:  v[0] = {r0c2, r1c2}, v[1].x = r2c2
             if constexpr (DOT) {
-                const double d0 = odd ? fmadd(v[j][1].x, x2, fmadd(v[j][0].y, x1, v[j][0].x * x0))
-                                      : fmadd(v[j][2].x, x2, fmadd(v[j][1].x, x1, v[j][0].x * x0));
-                const double d1 = fmadd(v[j][2].y, x2, fmadd(v[j][1].y, x1, v[j][0].y * x0));
+                const double d0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, (double)v[j][0].x * x0))
+                                      : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, (double)v[j][0].x * x0));
+                const double d1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, (double)v[j][0].y * x0));
                 acc0 = (live && !pad) ? acc0 + d0 : acc0;
                 acc1 = (live && !pad) ? acc1 + d1 : acc1;
             } else {
-                const double n0 = odd ? fmadd(v[j][1].x, x2, fmadd(v[j][0].y, x1, fmadd(v[j][0].x, x0, acc0)))
-                                      : fmadd(v[j][2].x, x2, fmadd(v[j][1].x, x1, fmadd(v[j][0].x, x0, acc0)));
-                const double n1 = fmadd(v[j][2].y, x2, fmadd(v[j][1].y, x1, fmadd(v[j][0].y, x0, acc1)));
+                const double n0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, fmadd((double)v[j][0].x, x0, acc0)))
+                                      : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, fmadd((double)v[j][0].x, x0, acc0)));
+                const double n1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, fmadd((double)v[j][0].y, x0, acc1)));
                 acc0 = live ? n0 : acc0;
                 acc1 = live ? n1 : acc1;
             }
@@ -956,7 +1023,8 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
     };
     uint32_t kA[NRS], kB[NRS], bA[NRS], bB[NRS];
     int nA[NRS], nB[NRS];
-    d2 vA[NRS][3], vB[NRS][3], xv[NRS];
+    s2 vA[NRS][3], vB[NRS][3];
+    d2 xv[NRS];
     load(R0, kA, bA, nA, vA);
     __builtin_amdgcn_s_waitcnt(0);
     for (int R = R0; R < R1; R += 2 * NRS) {
@@ -972,7 +1040,7 @@ __device__ __forceinline__ void run_pair(const SlotBin &b, int r, int lane, cons
     }
 }
 
-template <bool FASTE, int NB, bool KC, bool MASK = false, bool DOT = false>
+template <bool FASTE, int NB, bool KC, bool MASK = false, bool DOT = false, typename S = double>
 __global__ __launch_bounds__(kBlockThreads) void spmv_planar_pair(const SlotBin b,
                                                                   const double *__restrict__ x, double *__restrict__ y,
                                                                   double alpha, double beta, int rd_i)
@@ -988,7 +1056,7 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar_pair(const SlotBin 
 #ifndef VBC_PAIR_NRS
 #define VBC_PAIR_NRS 4  // run-rows per pipeline stage (ldoor stand-in: 2 -> 82, 3 -> 80, 4 -> 77 us)
 #endif
-    run_pair<VBC_PAIR_NRS, FASTE, NB, KC, MASK, DOT>(b, rg, lane, x, y, alpha, beta, rd_i != 0, lds, lds_out);
+    run_pair<VBC_PAIR_NRS, FASTE, NB, KC, MASK, DOT, S>(b, rg, lane, x, y, alpha, beta, rd_i != 0, lds, lds_out);
 }
 
 // Lane-pair streams (SlotBin::lanes with pair: fp64, 3-wide stripes, rows in runs of 3 -- FE-3D): the
@@ -1001,11 +1069,13 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar_pair(const SlotBin 
 // folds columns 0-1, the odd lane column 2, each in stored row order, and a LAST run stores them into
 // the wave's LDS tile buffer at the stream's current stripe slot.  After the loop the wave writes the
 // tile's outputs as one contiguous run (α, β applied there).
-template <int NRS, bool RD>
+// S: the stored value type (run_pair): S = float reads the run-row as 288 floats (pair_load).
+template <int NRS, bool RD, typename S = double>
 __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane, const double *__restrict__ x,
                                                double *__restrict__ y, double alpha, double beta, double *buf)
 {
     typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef S s2 __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(4))) const uint32_t *cptr;
     const int R0 = G(b.rrow)[r], R1 = G(b.rrow)[r + 1];
     if (R0 >= R1) return;
@@ -1014,24 +1084,22 @@ __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane
     const bool odd = (lane & 1) != 0;
     const int ps = lane >> 1;  // stream slot of the pair
     int cur = (int)G(b.lseg)[(size_t)r * 64 + ps];
-    const gptr<const double> val = G(static_cast<const double *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const double> xg = G(x);
     const cptr nlive = (cptr)b.nlive;
     const int o0 = 2 * lane, o1 = odd ? 192 + ps : 128 + 2 * ps, o2 = 224 + 2 * ps;
-    auto load = [&](int R, uint32_t (&kk)[NRS], int (&nl)[NRS], d2 (&v)[NRS][3]) {
+    auto load = [&](int R, uint32_t (&kk)[NRS], int (&nl)[NRS], s2 (&v)[NRS][3]) {
 #pragma unroll
         for (int j = 0; j < NRS; j++) {
             const int Rc = min(R + j, R1 - 1);
             nl[j] = (int)nlive[Rc];
             const bool dead = ps >= nl[j];  // dead pairs: pair 0's addresses (lane parity kept)
-            const int mps = dead ? 0 : ps;
+            const int mps = dead ? 0 : ps, mlane = dead ? (odd ? 1 : 0) : lane;
             const int m0 = dead ? (odd ? 2 : 0) : o0, m1 = dead ? (odd ? 192 : 128) : o1, m2 = dead ? 224 : o2;
             kk[j] = key[(size_t)Rc * 32 + mps];
-            const gptr<const double> rowp = val + (size_t)Rc * 288;
-            v[j][0] = __builtin_nontemporal_load((gptr<const d2>)(rowp + m0));
-            v[j][1] = *(const __attribute__((address_space(1))) d2 *)(rowp + m1);  // 8-B aligned (odd lanes)
-            v[j][2] = __builtin_nontemporal_load((gptr<const d2>)(rowp + m2));
+            const gptr<const S> rowp = val + (size_t)Rc * 288;
+            pair_load<S>(rowp, m0, m1, m2, odd, mlane, mps, v[j]);
         }
     };
     auto gather = [&](const uint32_t (&kk)[NRS], d2 (&xv)[NRS]) {
@@ -1042,7 +1110,7 @@ __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane
     double acc0 = 0.0, acc1 = 0.0;  // even: columns 0, 1; odd: column 2 in acc0
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
-    auto compute = [&](int R, const uint32_t (&kk)[NRS], const int (&nl)[NRS], const d2 (&v)[NRS][3],
+    auto compute = [&](int R, const uint32_t (&kk)[NRS], const int (&nl)[NRS], const s2 (&v)[NRS][3],
                        const d2 (&xv)[NRS]) {
 #pragma unroll
         for (int j = 0; j < NRS; j++) {
@@ -1056,11 +1124,12 @@ __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane
             const double other = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
             double x0 = odd ? other : xv[j].x, x1 = odd ? xv[j].x : xv[j].y, x2 = odd ? xv[j].y : other;
             if (kpad) x0 = x1 = x2 = 0.0;
+            const s2 r2 = pair_r2<S>(v[j]);
             // even: v[0] = {r0c0, r0c1}, v[1] = {r1c0, r1c1}, v[2] = {r2c0, r2c1}
             // odd:  v[0] = {r0c2, r1c2}, v[1].x = r2c2
-            const double n0 = odd ? fmadd(v[j][1].x, x2, fmadd(v[j][0].y, x1, fmadd(v[j][0].x, x0, acc0)))
-                                  : fmadd(v[j][2].x, x2, fmadd(v[j][1].x, x1, fmadd(v[j][0].x, x0, acc0)));
-            const double n1 = fmadd(v[j][2].y, x2, fmadd(v[j][1].y, x1, fmadd(v[j][0].y, x0, acc1)));
+            const double n0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, fmadd((double)v[j][0].x, x0, acc0)))
+                                  : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, fmadd((double)v[j][0].x, x0, acc0)));
+            const double n1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, fmadd((double)v[j][0].y, x0, acc1)));
             acc0 = live ? n0 : acc0;
             acc1 = live ? n1 : acc1;
             const bool fl = live && (kk[j] & kLast) != 0;
@@ -1078,7 +1147,8 @@ __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane
     };
     uint32_t kA[NRS], kB[NRS];
     int nA[NRS], nB[NRS];
-    d2 vA[NRS][3], vB[NRS][3], xv[NRS];
+    s2 vA[NRS][3], vB[NRS][3];
+    d2 xv[NRS];
     load(R0, kA, nA, vA);
     __builtin_amdgcn_s_waitcnt(0);
     for (int R = R0; R < R1; R += 2 * NRS) {
@@ -1120,7 +1190,7 @@ __device__ __forceinline__ void run_pair_lanes(const SlotBin &b, int r, int lane
     }
 }
 
-template <bool RD>
+template <bool RD, typename S = double>
 __global__ __launch_bounds__(kBlockThreads) void spmv_pair_lanes(const SlotBin b, const double *__restrict__ x,
                                                                  double *__restrict__ y, double alpha, double beta)
 {
@@ -1131,7 +1201,7 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_pair_lanes(const SlotBin b
 #ifndef VBC_PAIR_LANES_NRS
 #define VBC_PAIR_LANES_NRS 4  // run-rows per pipeline stage (as VBC_PAIR_NRS)
 #endif
-    run_pair_lanes<VBC_PAIR_LANES_NRS, RD>(b, rg, threadIdx.x & 63, x, y, alpha, beta, tilebuf[threadIdx.x >> 6]);
+    run_pair_lanes<VBC_PAIR_LANES_NRS, RD, S>(b, rg, threadIdx.x & 63, x, y, alpha, beta, tilebuf[threadIdx.x >> 6]);
 }
 
 // Split planar product (SlotBin::split = P > 1; ranges are single chunks): workgroup c = chunk c, wave k

@@ -10,6 +10,9 @@ namespace vbc {
 // vbc_planar_f64n.hip: spmv_planar / spmv_planar_fwd <double, ..., float> (bins with SlotBin::vsz = 4)
 int launch_planar_f64n(const SlotBin &hb, bool faste, bool staged, const void *x, void *y, double alpha, double beta,
                        bool rd, hipStream_t s);
+// vbc_pair_f64n.hip: spmv_planar_pair / spmv_pair_lanes <..., float> (lane-pair bins with SlotBin::vsz = 4)
+int launch_pair_f64n(const SlotBin &hb, bool faste, bool staged, const void *x, void *y, double alpha, double beta,
+                     bool rd, hipStream_t s);
 
 template <typename T, int W_, bool KC, int RUN>
 static void launch_w(const SlotBin &hb, const SlotBin *d_b, bool faste, bool staged, const void *x, void *y,
@@ -229,8 +232,10 @@ int launch_planar(int esz, const SlotBin &hb, const SlotBin *d_b, bool faste, bo
                   double alpha, double beta, bool rd, hipStream_t s)
 {
     if (hb.nranges <= 0) return (int)hipSuccess;
-    if (hb.vsz) {  // Float32 stored values on an fp64 handle (VBC_CREATE_NARROW_PLANAR): vbc_planar_f64n.hip
+    if (hb.vsz) {  // Float32 stored values on an fp64 handle (VBC_CREATE_NARROW_PLANAR): vbc_planar_f64n.hip;
+                   // lane-pair bins (VBC_CREATE_NARROW_PAIRS): vbc_pair_f64n.hip
         if (esz != 8) return (int)hipErrorInvalidValue;
+        if (hb.vsz == 4 && hb.pair) return launch_pair_f64n(hb, faste, staged, x, y, alpha, beta, rd, s);
         return launch_planar_f64n(hb, faste, staged, x, y, alpha, beta, rd, s);
     }
     if (hb.lanes && hb.pair) {  // lane-pair streams (B'x, fp64, w = 3, runs of 3)

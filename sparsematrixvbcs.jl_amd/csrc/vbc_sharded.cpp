@@ -695,9 +695,9 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
     if (flags & VBC_CREATE_NARROW_UPDATABLE)
         return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_UPDATABLE (with VBC_CREATE_NARROW_VALUES) is not supported on "
                                           "sharded handles");
-    if (flags & (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR))
-        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES / VBC_CREATE_NARROW_PLANAR are not supported on "
-                                          "sharded handles");
+    if (flags & (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS))
+        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES / VBC_CREATE_NARROW_PLANAR / VBC_CREATE_NARROW_PAIRS are "
+                                          "not supported on sharded handles");
     if (flags & VBC_CREATE_UPDATABLE)  // 3.3 callers rely on this refusal; the sharded flag is its own bit
         return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE is not supported on sharded handles "
                                           "(pass VBC_CREATE_UPDATABLE_SHARDS)");

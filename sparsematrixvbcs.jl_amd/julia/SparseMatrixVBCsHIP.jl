@@ -87,7 +87,8 @@ Device-resident copies of `B`, one libvbc handle per compute eltype met (created
 (VBC_CREATE_UPDATABLE) `update_values!(M, val)` overwrites the stored values in place.  With `narrow=true`
 (VBC_CREATE_NARROW_VALUES) a Float32 matrix applied to Float64 vectors keeps its values as Float32 on the
 device (slotted buckets; same bits as without); `narrow=:planar` (VBC_CREATE_NARROW_VALUES |
-VBC_CREATE_NARROW_PLANAR) also in the planar buckets of the plain planar kernels.  For any other eltype pair the
+VBC_CREATE_NARROW_PLANAR) also in the planar buckets of the plain planar kernels, `narrow=:pairs` (adds
+VBC_CREATE_NARROW_PAIRS) also in those of the lane-pair kernels.  For any other eltype pair the
 keyword is ignored; any other value, or `narrow` and `updatable` together, throw an ArgumentError.
 """
 mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
@@ -184,7 +185,7 @@ function handle_for(A::HIPMatrix, ::Type{Ty}) where {Ty}
     cdt == VBC_I64 && eltype(A) <: AbstractFloat && throw(InexactError(:convert, Ty, zero(eltype(A))))
     # narrow values: only Float32 values on a Float64 handle (the library refuses the flag for any other pair)
     flags = (eltype(A) === Float32 && cdt == VBC_F64) ? A.flags :
-            A.flags & ~(VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR)
+            A.flags & ~(VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS)
     get!(() -> _create(A.host, A.device, flags, cdt), A.handles, cdt)
 end
 
@@ -279,13 +280,18 @@ const VBC_CREATE_SERIAL = Cuint(8)
 const VBC_CREATE_UPDATABLE = Cuint(0x20)
 const VBC_CREATE_NARROW_VALUES = Cuint(0x80)  # Float32 values kept narrow on a Float64 handle (slotted buckets)
 const VBC_CREATE_NARROW_PLANAR = Cuint(0x100)  # only with 0x80: the plain planar buckets too
+const VBC_CREATE_NARROW_PAIRS = Cuint(0x400)  # only with 0x80 | 0x100: the lane-pair buckets too
 
-# the `narrow` keyword of the single-GPU constructors: false, true (0x80) or :planar (0x80 | 0x100)
+# the `narrow` keyword of the single-GPU constructors: false, true (0x80), :planar (0x80 | 0x100) or
+# :pairs (0x80 | 0x100 | 0x400)
 function narrow_flags(narrow, updatable::Bool)
     narrow === false && return Cuint(0)
-    narrow === true || narrow === :planar || throw(ArgumentError("narrow must be false, true or :planar"))
+    narrow === true || narrow === :planar || narrow === :pairs ||
+        throw(ArgumentError("narrow must be false, true, :planar or :pairs"))
     updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
-    return narrow === true ? VBC_CREATE_NARROW_VALUES : VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR
+    narrow === true && return VBC_CREATE_NARROW_VALUES
+    narrow === :planar && return VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR
+    return VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS
 end
 const VBC_CREATE_UPDATABLE_SHARDS = Cuint(0x40)  # the sharded creates only (they refuse 0x20)
 
