@@ -58,11 +58,13 @@ INT_OF = {8: np.int64, 4: np.int32}
 PROBLEMS = {}
 
 
-def problem(name, fp32=False, dirs=(True, False), multi=False):
-    """Register `fn() -> matrix` under `name`.  fp32: some GPU case runs the problem in Float32 (bound 2^24)."""
+def problem(name, fp32=False, dirs=(True, False), multi=False, cols=None):
+    """Register `fn() -> matrix` under `name`.  fp32: some GPU case runs the problem in Float32 (bound 2^24).
+    multi: X and Y0 are matrices of `cols` columns (default max(NRHS))."""
     def deco(fn):
-        assert name not in PROBLEMS
-        PROBLEMS[name] = dict(make=fn, limit=2.0 ** 24 if fp32 else 2.0 ** 53, dirs=dirs, multi=multi)
+        assert name not in PROBLEMS and (multi or cols is None)
+        PROBLEMS[name] = dict(make=fn, limit=2.0 ** 24 if fp32 else 2.0 ** 53, dirs=dirs, multi=multi,
+                              cols=(cols or max(NRHS)) if multi else 1)
         return fn
     return deco
 
@@ -87,7 +89,7 @@ def oracle_mul(B, val, x, y, alpha, beta, trans):
 
 
 class Solved:
-    """One problem: the matrix, and per direction x (nx or nx x 33), y0, the oracle's products for both
+    """One problem: the matrix, and per direction x (nx or nx x cols), y0, the oracle's products for both
     (alpha, beta) and the exactness bound max_i (|A||x| + |beta||y0|)_i."""
 
     def __init__(self, name):
@@ -97,7 +99,7 @@ class Solved:
         val = np.asarray(B.val, dtype=np.float64)
         assert np.array_equal(val, np.rint(val)) and np.abs(val).max() <= 8
         self.x, self.y0, self.ref, self.bound = {}, {}, {}, {}
-        cols = max(NRHS) if self.multi else 1
+        self.cols = cols = spec["cols"]
         for trans in spec["dirs"]:
             rng = np.random.default_rng(zlib.crc32(name.encode()) + int(trans))
             nx, ny = (B.m, B.n) if trans else (B.n, B.m)
@@ -242,6 +244,54 @@ problem("panel-w1to16-odd", fp32=True, multi=True)(
 problem("tiles-heights-odd", fp32=True, multi=True)(lambda: integer_values(_vbc2d_mixed_heights(
     np.random.default_rng(61), 301, 401, 1200, (3, 1, 4, 2, 3), (1, 3, 2, 4, 3), np.float64)))
 
+# merge layout at compile-time widths (VBC_SLOTS=0, VBC_SWEEP=0; stripes at most 8 wide), 70 columns: the fused
+# vector multi-RHS kernel (spmm_ranges / fixup_mm, row-major B'X) and, on column 0, spmv_ranges / fixup.
+#   fixed-w1to8, -odd: one merge bin per stored width (the per-bin carry slice and the bin lookup), 700 x 216 and
+#     701 x 217 (both extents odd);
+#   fixed-long: three 5-wide stripes of about 2100 stored rows each.  A range is one wave's share of a bin's tiles;
+#     build_bucket (csrc/vbc_device.hip) gives a bin nranges = min(round(target_ranges * its share of the entries),
+#     (ntiles + 1) / 2) ranges of tiles_per_range = ceil(ntiles / nranges) tiles, and a tile holds rpi * tile_k
+#     entries: rpi = 64 / 5 = 12 slots of tile_k = 4 (Float64) / 8 (Float32) entries.  The 6326 entries are 132 /
+#     66 tiles; target_ranges is CUs x occupancy x 4 >= 1024 on any gfx950 part, so nranges = 66 / 33 and
+#     tiles_per_range = 2: a range holds 96 / 192 entries, every stripe's segment crosses about 21 / 10 range
+#     boundaries, and most ranges hold no segment head at all.  Every output of the problem therefore comes from
+#     hand_mm / hand_off partials summed by fixup_mm / fixup;
+#   fixed-long-w1to8: two stripes of about 660 stored rows for each width 1..8, so every one of the 8 bins has
+#     two ranges or more (a range holds at most 2 tiles x 64 slots x 8 entries = 1024 entries, a bin about 1320):
+#     ranges of up to 512 entries cut both 660-entry segments, ranges of 1024 the second one.  Each bin's own slice
+#     of the carry buffer is written and read back;
+#   fixed-empty: 60 stored rows in 48 stripes, some of them empty: the fill list (beta * y, or 0, from fixup_mm).
+FIXED_COLS = 70
+FIXED = ("fixed-w1to8", "fixed-w1to8-odd", "fixed-long", "fixed-long-w1to8", "fixed-empty")
+problem("fixed-w1to8", fp32=True, multi=True, cols=FIXED_COLS)(
+    lambda: integer_values(V.synthetic.vbr_1dvbc(700, 48, 1500, np.arange(48) % 8 + 1, W=8, seed=5)))
+problem("fixed-w1to8-odd", fp32=True, multi=True, cols=FIXED_COLS)(
+    lambda: integer_values(V.synthetic.vbr_1dvbc(701, 49, 1500, np.arange(49) % 8 + 1, W=8, seed=5)))
+problem("fixed-long", fp32=True, multi=True, cols=FIXED_COLS)(
+    lambda: integer_values(V.synthetic.vbr_1dvbc(4000, 3, 9000, 5, W=8, seed=9)))
+problem("fixed-long-w1to8", fp32=True, multi=True, cols=FIXED_COLS)(
+    lambda: integer_values(V.synthetic.vbr_1dvbc(3001, 16, 12000, np.arange(16) % 8 + 1, W=8, seed=11)))
+
+
+@problem("fixed-empty", fp32=True, multi=True, cols=FIXED_COLS)
+def _fixed_empty():
+    B = V.synthetic.vbr_1dvbc(700, 48, 60, np.arange(48) % 8 + 1, W=8, seed=6)
+    empty = np.diff(B.pos) == 0
+    assert empty.any() and not empty.all()
+    return integer_values(B)
+
+
+# engine="vector" products that run one SpMV per column: matrices whose B'x layout is not merge-only (a golden
+# matrix under default knobs, the slotted mesh) or has a runtime-width bin (16-wide stripes), 5 columns
+PERCOL_COLS = 5
+PERCOL_GOLDEN = "LPnetlib__lp_blend"
+problem("percol-golden", fp32=True, multi=True, cols=PERCOL_COLS)(lambda: integer_values(
+    V.SparseMatrix1DVBC[8](golden_matrices()[PERCOL_GOLDEN]["A"], GOLDEN_METHODS["strict4"]())))
+problem("percol-slotted", fp32=True, multi=True, cols=PERCOL_COLS)(
+    lambda: integer_values(V.synthetic.fe_grid_2d(37, dof=2)))
+problem("percol-merge-w16", fp32=True, multi=True, cols=PERCOL_COLS)(
+    lambda: integer_values(V.synthetic.vbr_1dvbc(900, 300, 1800, 16, W=16, seed=16)))
+
 
 @pytest.mark.parametrize("name", sorted(PROBLEMS))
 def test_inputs_are_exact(name):
@@ -303,9 +353,11 @@ def _outside(itemsize, off, shape, ld, layout):
     return m
 
 
-def product_checked(op, x, xoff, y_start, yoff, ref, alpha, beta, what, xbuf=None, ld=(None, None), layout="R"):
+def product_checked(op, x, xoff, y_start, yoff, ref, alpha, beta, what, xbuf=None, ld=(None, None), layout="R",
+                    engine="auto", call=None):
     """One product on embedded operands and its three checks.  x, y_start, ref: host arrays in the operand eltype
-    (ref in float64).  Returns the embedded x so that a caller can reuse it."""
+    (ref in float64).  The product is V.mul_(..., engine=engine), or call(y_view, x_view, alpha, beta) when given.
+    Returns the embedded x so that a caller can reuse it."""
     dt = y_start.dtype
     if xbuf is None:
         xbuf = embed(x, xoff, float("nan") if dt.kind == "f" else X_CANARY_INT, ld[0], layout)
@@ -313,7 +365,10 @@ def product_checked(op, x, xoff, y_start, yoff, ref, alpha, beta, what, xbuf=Non
     if beta == 0 and dt.kind == "f":
         y_start = np.full_like(y_start, np.nan)
     ybuf, yv = embed(y_start, yoff, canary, ld[1], layout)
-    V.mul_(yv, op, xbuf[1], alpha, beta)
+    if call is None:
+        V.mul_(yv, op, xbuf[1], alpha, beta, engine=engine)
+    else:
+        call(yv, xbuf[1], alpha, beta)
     got = yv.cpu().numpy()
     if dt.kind == "f":
         assert np.isfinite(got).all(), (what, "non-finite values in the window")
@@ -590,6 +645,43 @@ def test_merge_runtime_width(monkeypatch, name, dt):
         sweep_vector(M, s, trans, dt, "merge")
 
 
+class Column:
+    """Column j of a multi-RHS problem as a single-vector problem (what sweep_vector takes)."""
+
+    def __init__(self, s, j=0):
+        self.name = s.name
+        self.x = {t: np.ascontiguousarray(X[:, j]) for t, X in s.x.items()}
+        self.y0 = {t: np.ascontiguousarray(Y[:, j]) for t, Y in s.y0.items()}
+        self.ref = {t: {ab: np.ascontiguousarray(r[:, j]) for ab, r in refs.items()} for t, refs in s.ref.items()}
+
+
+MERGE_FIXED_KNOBS = {"VBC_SLOTS": "0", "VBC_SWEEP": "0", "VBC_FWD_T": "0"}
+
+
+def check_merge_fixed(M, trans):
+    """The handle's layout is merge-only and every stripe at most 8 wide: every bin has a compile-time width."""
+    assert np.diff(M.Phi.spl).max() <= 8
+    inf = M.info(trans=trans)
+    assert inf["bins_t" if trans else "bins_f"] > 0, inf
+    assert inf["slot_bins"] == 0 and inf["sweep_bins"] == 0 and inf["planar_bins"] == 0, inf
+
+
+@gpu
+@F32_F64
+@pytest.mark.parametrize("name", ["fixed-w1to8", "fixed-w1to8-odd", "fixed-long", "fixed-long-w1to8"])
+def test_merge_fixed_width(monkeypatch, name, dt):
+    """spmv_ranges<T, 0 | 1, K, P> at compile-time widths, both directions (the forward product as merge bins of
+    B, VBC_FWD_T=0): the load-free writer at beta = 0, the reading one at beta = 2, and fixup on segments that
+    span ranges (fixed-long: every B'x output).  Stored widths are the padded ones -- Float64 1, 2, 4, 4, 5, 6, 8,
+    8 and Float32 1, 2, 4, 4, 5, 8, 8, 8 for stripes 1..8 wide -- so wkey 3 and 7 (and Float32 6) have no bin."""
+    setenvs(monkeypatch, MERGE_FIXED_KNOBS)
+    s = Column(solve(name))
+    M = fresh(solve(name).B, dt)
+    for trans in (True, False):
+        check_merge_fixed(M, trans)
+        sweep_vector(M, s, trans, dt, "merge, fixed widths")
+
+
 @gpu
 @pytest.mark.parametrize("name", list(CSC_SCALES))
 def test_csc_trspmv_blocked_columns_fp32(name):
@@ -691,3 +783,188 @@ def test_multi_rhs_tiles(monkeypatch, name, dt, trans, nobuf):
     inf = M.info(trans=trans, multi=True)
     assert inf["bins_m"] > 0 and inf["planar_mask"] & 512, inf
     sweep_multi(M, s, trans, dt, ("tiles", "nobuf", nobuf))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# engine="vector": the fused vector kernel, the per-column branches, vbc_mul_mat_ex on an Int64 handle
+# ---------------------------------------------------------------------------------------------------------------
+
+FUSED_NRHS = (2, 16, 17, 64, 65, 70)  # NR = 16 (2, 16), NR = 64 (17, 64), a second chunk of 1 and of 6 columns
+
+
+def sweep_fused(M, s, dt, what):
+    """Row-major B'X, engine="vector": every nrhs of FUSED_NRHS at ld = nrhs + 1 and nrhs + 5, X and Y at base
+    offsets 0 and 1, both (alpha, beta); then 16 contiguous right-hand sides (ld = 16) at both offsets."""
+    dt = np.dtype(dt)
+    op = V.adjoint(M)
+    X, Y0 = s.x[True].astype(dt), s.y0[True].astype(dt)
+    cases = [(nrhs, nrhs + e) for nrhs in FUSED_NRHS for e in (1, 5)] + [(16, 16)]
+    for nrhs, ld in cases:
+        Xn, Yn = np.ascontiguousarray(X[:, :nrhs]), np.ascontiguousarray(Y0[:, :nrhs])
+        refs = {ab: np.ascontiguousarray(r[:, :nrhs]) for ab, r in s.ref[True].items()}
+        for xo in (0, 1):
+            xbuf = None
+            for yo in (0, 1):
+                for alpha, beta in AB:
+                    xbuf = product_checked(op, Xn, xo, Yn, yo, refs[(alpha, beta)], alpha, beta,
+                                           (s.name, what, "nrhs", nrhs, "ld", ld, "X+", xo, "Y+", yo, alpha, beta),
+                                           xbuf, (ld, ld), "R", engine="vector")
+
+
+@gpu
+@F32_F64
+@pytest.mark.parametrize("name", FIXED)
+def test_fused_vector_multi_rhs(monkeypatch, name, dt):
+    """spmm_ranges<T, 16 | 64, K> and fixup_mm<T, 16 | 64>: row-major B'X with engine="vector" on a merge-only
+    layout of compile-time widths (mul_mat_device's `fused` branch).  One bin per stored width (each bin its own
+    slice of the carry buffer, a quarter as long at NR = 16), segments that span ranges (fixed-long: hand_mm and
+    fixup_mm produce every output), empty stripes (fixed-empty: fixup_mm's fill list), a second 64-column chunk."""
+    setenvs(monkeypatch, MERGE_FIXED_KNOBS)
+    s = solve(name)
+    assert s.cols == FIXED_COLS >= max(FUSED_NRHS)
+    M = fresh(s.B, dt)
+    check_merge_fixed(M, True)
+    sweep_fused(M, s, dt, "fused vector")
+
+
+PERCOL_NRHS = (2, 5)
+
+
+def sweep_per_column(M, s, trans, dt, what, layouts=("R", "C")):
+    """engine="vector", nrhs 2 and 5, row- and column-major, ld = extent + 1 and extent + 5, X and Y at base offsets
+    0 and 1, both (alpha, beta).  Row-major: the columns go through the handle's contiguous temporaries by strided
+    copies (beta = 2 reads Y through them), so the gap columns of Y must keep the canary."""
+    dt = np.dtype(dt)
+    op = V.adjoint(M) if trans else M
+    X, Y0 = s.x[trans].astype(dt), s.y0[trans].astype(dt)
+    nx, ny = X.shape[0], Y0.shape[0]
+    for nrhs in PERCOL_NRHS:
+        Xn, Yn = np.ascontiguousarray(X[:, :nrhs]), np.ascontiguousarray(Y0[:, :nrhs])
+        refs = {ab: np.ascontiguousarray(r[:, :nrhs]) for ab, r in s.ref[trans].items()}
+        for layout in layouts:
+            for e in (1, 5):
+                ld = (nrhs + e, nrhs + e) if layout == "R" else (nx + e, ny + e)
+                for xo in (0, 1):
+                    xbuf = None
+                    for yo in (0, 1):
+                        for alpha, beta in AB:
+                            xbuf = product_checked(op, Xn, xo, Yn, yo, refs[(alpha, beta)], alpha, beta,
+                                                   (s.name, what, "trans", trans, "nrhs", nrhs, layout, "ld", ld,
+                                                    "X+", xo, "Y+", yo, alpha, beta), xbuf, ld, layout,
+                                                   engine="vector")
+
+
+# problem -> (knobs, what vbc_info must say about the B'x handle)
+PERCOL_CASES = {
+    "percol-golden": ({}, lambda inf: inf["slot_bins"] > 0),                     # default knobs: not merge-only
+    "percol-slotted": ({"VBC_SLOTS": "1"}, lambda inf: inf["slot_bins"] > 0),
+    # merge-only, but the 16-wide stripes' bin has a runtime width (wkey = 0): no fused kernel
+    "percol-merge-w16": ({"VBC_SLOTS": "0"}, lambda inf: inf["bins_t"] > 0 and inf["slot_bins"] == 0 and
+                         inf["sweep_bins"] == 0 and inf["planar_bins"] == 0),
+}
+
+
+@gpu
+@TRANS
+@F32_F64
+@pytest.mark.parametrize("name", list(PERCOL_CASES))
+def test_vector_engine_per_column(monkeypatch, name, dt, trans):
+    """vbc_mul_mat without panels and without the fused kernel: one SpMV per column.  Row-major operands go through
+    staging buffers 2 / 3 (copy2d), column-major ones are passed column by column; B'X on layouts the fused kernel
+    does not read, and B X (always per column)."""
+    knobs, layout_ok = PERCOL_CASES[name]
+    setenvs(monkeypatch, knobs)
+    s = solve(name)
+    M = fresh(s.B, dt)
+    inf = M.info(trans=True)
+    assert layout_ok(inf), inf
+    if name == "percol-merge-w16":
+        assert np.diff(M.Phi.spl).max() == 16
+    assert M.info(trans=trans)["bins_m"] == 0  # (the vector handle: no panel layout)
+    sweep_per_column(M, s, trans, dt, "per column")
+
+
+@gpu
+@F32_F64
+def test_vector_engine_column_major_on_fixed_merge(monkeypatch, dt):
+    """Column-major operands never take the fused kernel, even on the layout it reads: the per-column loop on
+    fixed-w1to8-odd, both directions."""
+    setenvs(monkeypatch, MERGE_FIXED_KNOBS)
+    s = solve("fixed-w1to8-odd")
+    M = fresh(s.B, dt)
+    for trans in (True, False):
+        check_merge_fixed(M, trans)
+        sweep_per_column(M, s, trans, dt, "column-major on the fused layout", layouts=("C",))
+
+
+def dense_int(B):
+    """B as a dense Int64 array, column by column through the oracle (small integer values: exact)."""
+    val = np.asarray(B.val, dtype=np.float64)
+    D = np.empty((B.m, B.n), np.int64)
+    for j in range(B.n):
+        e = np.zeros(B.n)
+        e[j] = 1.0
+        D[:, j] = oracle_mul(B, val, e, np.zeros(B.m), 1.0, 0.0, False).astype(np.int64)
+    return D
+
+
+def int64_operands(B, trans, nrhs=3):
+    rng = np.random.default_rng(64 + int(trans))
+    nx, ny = (B.m, B.n) if trans else (B.n, B.m)
+    return rng.integers(-8, 9, (nx, nrhs)).astype(np.int64), rng.integers(-8, 9, (ny, nrhs)).astype(np.int64)
+
+
+@gpu
+@pytest.mark.parametrize("layout", ["R", "C"])
+@pytest.mark.parametrize("kind", ["bool", "i32"])
+def test_mul_mat_ex_int64(kind, layout):
+    """vbc_mul_mat_ex on an Int64 handle, called directly (the Python mirror loops over the columns itself): 3
+    right-hand sides, (alpha, beta) = (3, -2), against numpy's Int64 product (test_gpu_eltypes.py::expected)."""
+    B = solve(f"int64-{kind}").B
+    M = fresh(B, np.int64)
+    D = dense_int(B)
+    alpha, beta = 3, -2
+    for trans in (True, False):
+        h = M.handle(0, trans, compute=L.VBC_I64)
+        assert M.info(trans=trans, compute=L.VBC_I64)["dtype"] == L.VBC_I64
+        X, Y0 = int64_operands(B, trans)
+        ref = alpha * ((D.T if trans else D) @ X) + beta * Y0  # Int64, wrapping
+        nx, ny, nrhs = X.shape[0], Y0.shape[0], X.shape[1]
+        for e in (1, 5):
+            ld = (nrhs + e, nrhs + e) if layout == "R" else (nx + e, ny + e)
+
+            def call(yv, xv, a, b, ld=ld):
+                stream = torch.cuda.current_stream(yv.device).cuda_stream
+                L.check(L.lib().vbc_mul_mat_ex(h, int(trans), nrhs, xv.data_ptr(), L.VBC_I64, ld[0], nx, yv.data_ptr(),
+                                               L.VBC_I64, ld[1], ny, float(a), float(b), L.VBC_MEM_DEVICE, stream,
+                                               L.VBC_MAT_ROWMAJOR if layout == "R" else 0), "vbc_mul_mat_ex")
+
+            for xo in (0, 1):
+                for yo in (0, 1):
+                    product_checked(None, X, xo, Y0, yo, ref, alpha, beta,
+                                    (kind, "mul_mat_ex", "trans", trans, layout, "ld", ld, "X+", xo, "Y+", yo),
+                                    None, ld, layout, call=call)
+
+
+@gpu
+@pytest.mark.parametrize("layout", ["R", "C"])
+def test_mul_mat_ex_int64_refuses_int32_y(layout):
+    """Y_dtype = VBC_I32 on an Int64 handle: VBC_UNSUPPORTED_DTYPE, and no element of Y's allocation changes."""
+    B = solve("int64-i32").B
+    M = fresh(B, np.int64)
+    for trans in (True, False):
+        h = M.handle(0, trans, compute=L.VBC_I64)
+        X, Y0 = int64_operands(B, trans)
+        nx, ny, nrhs = X.shape[0], Y0.shape[0], X.shape[1]
+        ld = (nrhs + 1, nrhs + 1) if layout == "R" else (nx + 1, ny + 1)
+        _, xv = embed(X, 1, X_CANARY_INT, ld[0], layout)
+        ybuf, yv = embed(Y0.astype(np.int32), 1, Y_CANARY[4], ld[1], layout)
+        before = ybuf.clone()
+        stream = torch.cuda.current_stream(yv.device).cuda_stream
+        st = L.lib().vbc_mul_mat_ex(h, int(trans), nrhs, xv.data_ptr(), L.VBC_I64, ld[0], nx, yv.data_ptr(), L.VBC_I32,
+                                    ld[1], ny, 3.0, -2.0, L.VBC_MEM_DEVICE, stream,
+                                    L.VBC_MAT_ROWMAJOR if layout == "R" else 0)
+        assert st == L.VBC_UNSUPPORTED_DTYPE, (st, L.last_error())
+        torch.cuda.synchronize()
+        assert torch.equal(ybuf, before), (layout, trans)
+        assert np.array_equal(yv.cpu().numpy(), Y0.astype(np.int32))

@@ -228,20 +228,23 @@ def test_integer_valued_exact():
     assert np.array_equal(y.cpu().numpy(), D @ xf)
 
 
-def test_multi_rhs_columnwise(golden):
+@pytest.mark.parametrize("engine", ["auto", "vector"])
+def test_multi_rhs_columnwise(golden, engine):
+    """16 column-major right-hand sides, host and device operands.  engine="auto": the matrix-core panels (16 >=
+    MFMA_MIN_RHS columns build a multi handle); engine="vector": the SpMV handle, one product per column."""
     A = golden["LPnetlib__lp_blend"]["A"]
     m, n = A.shape
     B = V.SparseMatrix1DVBC[4](A, V.StrictChunker(4))
     rng = np.random.default_rng(4)
     X = np.asfortranarray(rng.uniform(-1, 1, (m, 16)))
     Y = np.asfortranarray(np.zeros((n, 16)))
-    V.mul_(Y, B.T, X)
+    V.mul_(Y, B.T, X, engine=engine)
     R = O.Ref1DVBC(m, n, 4, B.Phi.spl, B.pos, B.idx, B.ofs, B.val)
     Yr = O.mulmat_t(R, X, np.asfortranarray(np.zeros((n, 16))))
     assert rel(Y, Yr) <= TOL64
     Xd = torch.from_numpy(np.ascontiguousarray(X.T)).to(DEV).T   # column-major view
     Yd = torch.zeros((16, n), dtype=torch.float64, device=DEV).T
-    V.mul_(Yd, B.T, Xd)
+    V.mul_(Yd, B.T, Xd, engine=engine)
     assert rel(Yd.cpu().numpy(), Yr) <= TOL64
 
 
@@ -284,11 +287,18 @@ def test_north_star_size_independent_properties():
     assert abs(lhs - rhs) <= 1e-9 * torch.linalg.norm(r).item() * torch.linalg.norm(x1).item()
 
 
-@pytest.mark.parametrize("nrhs", [2, 3, 16, 17, 40, 70])
-@pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_multi_rhs_rowmajor(nrhs, dtype):
-    """Fused multi-RHS kernel (row-major X / Y) vs the oracle applied column by column, with
-    alpha/beta, mixed widths 1..8 (fused) and a w > 8 bucket (per-column fallback), both directions."""
+# (the engine="auto" cases keep the ids they had before the engine parameter: [float64-2] ...)
+@pytest.mark.parametrize(
+    "dtype,nrhs,engine",
+    [pytest.param(dt, nrhs, engine, id=f"{dt.__name__}-{nrhs}" + ("" if engine == "auto" else f"-{engine}"))
+     for engine in ("auto", "vector") for dt in (np.float64, np.float32) for nrhs in (2, 3, 16, 17, 40, 70)])
+def test_multi_rhs_rowmajor(nrhs, dtype, engine):
+    """Row-major X / Y vs the oracle applied column by column, with alpha/beta, mixed widths 1..8, one width and a
+    w > 8 bucket, both directions.  engine="auto": every nrhs here is >= MFMA_MIN_RHS, so the product builds a multi
+    handle and runs the matrix-core panels.  engine="vector": the SpMV handle; under default knobs these small
+    matrices get planar / fused-split buckets, so B'X runs the per-column fallback through the handle's column
+    temporaries (as B X always does), not the fused vector kernel -- that one is held to the oracle by
+    test_gpu_operand_views.py::test_fused_vector_multi_rhs."""
     tol = TOL64 if dtype == np.float64 else TOL32
     rng = np.random.default_rng(nrhs)
     for widths in ([1, 2, 3, 4, 5, 6, 7, 8], [4], [2, 12]):
@@ -302,10 +312,10 @@ def test_multi_rhs_rowmajor(nrhs, dtype):
             X = rng.uniform(-1, 1, (nx, nrhs)).astype(dtype)
             Y0 = rng.uniform(-1, 1, (ny, nrhs)).astype(dtype)
             Yd = dev(Y0)
-            V.mul_(Yd, V.adjoint(B) if trans else B, dev(X), 1.5, 0.5)
+            V.mul_(Yd, V.adjoint(B) if trans else B, dev(X), 1.5, 0.5, engine=engine)
             ref = np.stack([O.mul(R, X[:, j].astype(np.float64), Y0[:, j].astype(np.float64), 1.5, 0.5,
                                   trans=trans, ref_semantics=False) for j in range(nrhs)], axis=1)
-            assert rel(Yd.cpu().numpy(), ref) <= tol, (widths, trans, nrhs)
+            assert rel(Yd.cpu().numpy(), ref) <= tol, (widths, trans, nrhs, engine)
 
 
 def test_multi_rhs_vbc2d_golden(golden):
