@@ -28,7 +28,8 @@
  * vbc_sharded_update_values (vbc_info unchanged by both).  VBC_CREATE_NARROW_VALUES came without a version
  * bump (vbc_version() still returns 30400, no new symbol): a binding detects the capability by a create with
  * the flag succeeding and by vbc_info.planar_mask bits 12 / 13; a library without it refuses nothing and
- * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15; VBC_CREATE_NARROW_PAIRS: bits 16 / 17. */
+ * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15; VBC_CREATE_NARROW_PAIRS: bits 16 / 17;
+ * VBC_CREATE_NARROW_STREAMS: bits 18 / 19. */
 #define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
@@ -199,6 +200,31 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       creates without vbc_types, any other eltype pair, both sharded creates with or
                                       without VBC_CREATE_UPDATABLE_SHARDS).  No version bump and no new symbol, as
                                       with 0x80 / 0x100: a binding detects the capability by bits 16 / 17; a library
+                                      without it ignores the bit. */
+
+#define VBC_CREATE_NARROW_STREAMS 0x800u /* Only together with VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR and
+                                      VBC_CREATE_NARROW_PAIRS (0xD80; so on the *_ex creates with Float32 values on a
+                                      Float64 handle): the handle does everything 0x580 does and also keeps Float32
+                                      values in every bucket spmv_planar_lanes runs -- the per-lane compacted streams
+                                      of B'x and the forward lane streams (a node block's rows and columns exchanged),
+                                      the layout the planner picks by itself for irregular node-blocked operators
+                                      (FE-3D).  A narrow stored row holds the wide one's 64 * w values as 64 * w floats
+                                      in the Float32 column-group arrangement of 0x100 (16-B groups of four floats, the
+                                      last group narrower; rows 16-B aligned), rows in the same order; a lane widens
+                                      each value as the operand of the multiply-add that folds it.  As with 0x80 /
+                                      0x100 / 0x400 no layout decision changes -- tile size, stream cut, keys and
+                                      launch groups are those of the wide handle -- and every product is bit-identical
+                                      to that of the handle created with 0x580 (and so to the wide handle's).  The split
+                                      and fused-split kernels keep Float64 values; so do the swept, merge and panel /
+                                      tile layouts.  vbc_info.planar_mask bit 18 / 19 say whether a B'x / forward
+                                      lane-stream bucket stores Float32 (bits 14 - 17 keep their meaning); bytes_t,
+                                      bytes_f and device_bytes count the bytes really stored.  May be combined with
+                                      VBC_CREATE_NARROW_UPDATABLE.  Refused (VBC_INVALID_ARG, no device work, no
+                                      handle): 0x800 without any one of 0x80, 0x100, 0x400, 0x800 together with
+                                      VBC_CREATE_UPDATABLE (0x20), and every create that refuses 0x80 (the creates
+                                      without vbc_types, any other eltype pair, both sharded creates with or without
+                                      VBC_CREATE_UPDATABLE_SHARDS).  No version bump and no new symbol, as with 0x80 /
+                                      0x100 / 0x400: a binding detects the capability by bits 18 / 19; a library
                                       without it ignores the bit. */
 
 /* mul flags */
@@ -487,7 +513,9 @@ typedef struct vbc_info {
                                planar bucket (spmv_planar) stores Float32 values (VBC_CREATE_NARROW_PLANAR),
                                bit 15: some forward planar bucket (spmv_planar_fwd) does; bit 16: some B'x
                                lane-pair bucket (spmv_planar_pair, spmv_pair_lanes) stores Float32 values
-                               (VBC_CREATE_NARROW_PAIRS), bit 17: some forward lane-pair bucket does */
+                               (VBC_CREATE_NARROW_PAIRS), bit 17: some forward lane-pair bucket does; bit 18: some
+                               B'x lane-stream bucket (spmv_planar_lanes) stores Float32 values
+                               (VBC_CREATE_NARROW_STREAMS), bit 19: some forward lane-stream bucket does */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

@@ -954,8 +954,10 @@ static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const 
     const int64_t vals_per_row = pair ? 288 : (int64_t)64 * w;
     const int64_t keys_per_row = NS;
     // VBC_CREATE_NARROW_PAIRS (build_slots): the lane-pair streams store floats, run-rows of 288 (put_pair_run);
-    // everything above was decided with esz.  Plain lane streams stay wide.
-    const bool narrow = pair && h->narrow_pairs;
+    // everything above was decided with esz.  VBC_CREATE_NARROW_STREAMS: so do the plain lane streams (B'x and,
+    // through build_fwd_lanes, forward), their rows in the Float32 column-group arrangement (planar_off(4, ...), rows
+    // of 64 * w floats: 16-B aligned) -- S, smax, the tile count, nr_target and the stream cut above used esz.
+    const bool narrow = esz == 8 && (pair ? h->narrow_pairs : h->narrow_streams);
     const int vsz = narrow ? 4 : esz;
     b.vsz = narrow ? 4 : 0;
     ps.o_val = ar.reserve((size_t)rows * vals_per_row * vsz);
@@ -1009,9 +1011,12 @@ static int build_lanes(PlanCtx *h, int w, const std::vector<Entry> &ents, const 
                     }
                     for (int d = 0; d < run; d++) {
                         const Entry &en = ents[sbeg[q] + u * run + d];
-                        char *rowp = vv + (row0 + d) * 64 * w * esz;
-                        for (int cc = 0; cc < w; cc++)
-                            std::memcpy(rowp + planar_off(esz, w, l, cc) * esz, val + (en.voff + cc) * esz, (size_t)esz);
+                        char *rowp = vv + (row0 + d) * 64 * w * vsz;
+                        for (int cc = 0; cc < w; cc++) {
+                            char *dst = rowp + planar_off(vsz, w, l, cc) * vsz;
+                            if (narrow) narrow_value(h, reinterpret_cast<const double *>(val) + en.voff + cc, dst);
+                            else std::memcpy(dst, val + (en.voff + cc) * esz, (size_t)esz);
+                        }
                     }
                 }
             }
@@ -2042,7 +2047,7 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                 commit_launch_keys(h, one, ar);
                 const PendingSlot &p1 = one[0];
                 if (lanes)  // real values, one key per block, nlive per row, the tile tables, y
-                    h->st.bytes_f += p1.real * (int64_t)R * h->esz + p1.key_bytes + p1.rows * 4 +
+                    h->st.bytes_f += p1.real * (int64_t)R * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes + p1.rows * 4 +
                                   (int64_t)p1.b.ntiles * (8 + 128) + s.m * h->esz;
                 else if (fpair)  // run-rows of 32 blocks (288 values), one key per block, y
                     h->st.bytes_f += p1.rows * 288 * (int64_t)(p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes + (p1.b.mask ? p1.rows * 4 : 0) +
@@ -3035,6 +3040,7 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
                                   (rec ? rec->ft_narrow : all_float_exact(cv.data(), (int64_t)(cv.size() / 8)));
             cfg_c.narrow_planar = cfg.narrow_planar && cfg_c.narrow_values;
             cfg_c.narrow_pairs = cfg.narrow_pairs && cfg_c.narrow_planar;
+            cfg_c.narrow_streams = cfg.narrow_streams && cfg_c.narrow_pairs;
             h->st.ft_narrow = cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
             st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
@@ -3304,7 +3310,15 @@ static int refuse_narrow_flag(vbc_handle **out, const char *why)
     if (out) *out = nullptr;
     return fail(VBC_INVALID_ARG, why);
 }
-constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS;
+constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS |
+                                 VBC_CREATE_NARROW_STREAMS;
+constexpr unsigned kNarrowBelowStreams = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS;
+constexpr const char *kNarrowStreamsAlone = "VBC_CREATE_NARROW_STREAMS is valid only together with VBC_CREATE_NARROW_VALUES, "
+                                            "VBC_CREATE_NARROW_PLANAR and VBC_CREATE_NARROW_PAIRS";
+constexpr const char *kNarrowStreamsPlain = "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR "
+                                            "and VBC_CREATE_NARROW_PAIRS) needs Float32 values on a Float64 handle: pass it "
+                                            "to vbc1d_create_ex / vbc2d_create_ex / vbc_csc_create_ex (the creates without "
+                                            "vbc_types store the compute eltype)";
 constexpr const char *kNarrowPairsAlone = "VBC_CREATE_NARROW_PAIRS is valid only together with VBC_CREATE_NARROW_VALUES and "
                                           "VBC_CREATE_NARROW_PLANAR";
 constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR / VBC_CREATE_NARROW_PAIRS with it) needs Float32 values "
@@ -3371,6 +3385,7 @@ static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t 
                      int64_t nval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
@@ -3458,6 +3473,7 @@ static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t 
                      int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
@@ -3563,6 +3579,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
                       const void *nzval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
     std::vector<char> bv;
@@ -3594,6 +3611,8 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
     flags &= ~VBC_CREATE_NARROW_UPDATABLE;  // (it changes no layout)
     const unsigned narrow = flags & kNarrowBits;
+    if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
+        return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
@@ -3631,6 +3650,8 @@ int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const 
     if (int st = stripes(nullptr, in, sv)) return st;
     flags &= ~(VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS | VBC_CREATE_NARROW_UPDATABLE);
     const unsigned narrow = flags & kNarrowBits;
+    if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
+        return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
     if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
@@ -3659,6 +3680,14 @@ int vbc_destroy(vbc_handle *h)
 {
     release(h);
     return VBC_OK;
+}
+
+// The planar_mask bit of a planar bucket of Float32 values: 14 / 15 a B'x / forward bucket of the plain planar
+// kernels (VBC_CREATE_NARROW_PLANAR), 16 / 17 a lane-pair one (VBC_CREATE_NARROW_PAIRS), 18 / 19 a plain lane-stream
+// one (VBC_CREATE_NARROW_STREAMS).
+static int narrow_bit(const SlotBin &b, bool fwd)
+{
+    return (b.pair ? 16 : b.lanes ? 18 : 14) + (fwd ? 1 : 0);
 }
 
 int vbc_get_info(const vbc_handle *h, vbc_info *info)
@@ -3736,15 +3765,14 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
             if (b.vsz) info->planar_mask |= 1 << 13;
     if (h->has_t)
         for (const SlotBin &b : h->lt.pbins)
-            if (b.vsz) info->planar_mask |= 1 << (b.pair ? 16 : 14);  // B'x planar buckets of Float32 values (VBC_CREATE_NARROW_
-                                                                      // PLANAR); lane-pair ones (VBC_CREATE_NARROW_PAIRS)
+            if (b.vsz) info->planar_mask |= 1 << narrow_bit(b, false);
     if (h->has_f)
         for (const auto &l : h->lf)
             for (const SlotBin &b : l.pbins)
-                if (b.vsz) info->planar_mask |= 1 << (b.pair ? 17 : 15);  // forward ones
+                if (b.vsz) info->planar_mask |= 1 << narrow_bit(b, true);
     if (h->has_ft)
         for (const SlotBin &b : h->lft.pbins)
-            if (b.vsz) info->planar_mask |= 1 << (b.pair ? 17 : 15);
+            if (b.vsz) info->planar_mask |= 1 << narrow_bit(b, true);
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3983,6 +4011,16 @@ static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, u
     narrow = 0;
     const bool upd = (flags & VBC_CREATE_NARROW_UPDATABLE) != 0;  // (its refusals name it)
     if (!(flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE))) return VBC_OK;
+    if (flags & VBC_CREATE_NARROW_STREAMS) {  // (its refusals name it too, whatever else is set)
+        if ((flags & kNarrowBelowStreams) != kNarrowBelowStreams) return refuse_narrow_flag(out, kNarrowStreamsAlone);
+        if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
+            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES) needs val_dtype VBC_F32 "
+                                           "and compute_dtype VBC_F64");
+        if (flags & VBC_CREATE_UPDATABLE)
+            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES) cannot be combined with "
+                                           "VBC_CREATE_UPDATABLE: a narrow handle is made updatable by "
+                                           "VBC_CREATE_NARROW_UPDATABLE instead");
+    }
     if (upd && !(flags & VBC_CREATE_NARROW_VALUES))
         return refuse_narrow_flag(out, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
     if ((flags & VBC_CREATE_NARROW_PAIRS) && (flags & (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR)) !=

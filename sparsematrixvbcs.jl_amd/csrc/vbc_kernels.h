@@ -146,7 +146,9 @@ struct SlotBin {
                            // widened in registers, every bin of the launch alike); 0 = values of the compute eltype.
                            // Planar (VBC_CREATE_NARROW_PLANAR; spmv_planar / spmv_planar_fwd bins only, never plain
                            // lanes or split): 4 = chunk rows in the Float32 column-group arrangement, planar_off(4, ..).
-                           // Pair (VBC_CREATE_NARROW_PAIRS; spmv_planar_pair / spmv_pair_lanes): 4 = run-rows of 288 floats
+                           // Pair (VBC_CREATE_NARROW_PAIRS; spmv_planar_pair / spmv_pair_lanes): 4 = run-rows of 288 floats.
+                           // Plain lanes (VBC_CREATE_NARROW_STREAMS; spmv_planar_lanes): 4 = rows of 64 * w floats,
+                           // planar_off(4, ..)
 };
 
 // Runs with holes (SlotBin::holes): the run's stored-row mask above the gather index of its first key.

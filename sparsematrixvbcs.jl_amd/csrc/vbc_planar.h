@@ -376,13 +376,18 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar(const SlotBin b, co
 // lanes measured 213 -> 275 us on FE-3D: partial-line writes; no global store sits inside the loop,
 // so the compiler's vmcnt accounting stays exact.)  DEEP: keys two steps ahead, the gathers one step
 // ahead of their fold.
+// S: the stored value type (default T).  S = float on T = double (VBC_CREATE_NARROW_STREAMS): a stored row is
+// 64 * W_ floats in the Float32 column-group arrangement (planar_off(4, ...), as run_planar's), so a lane's value
+// loads are those of the fp32 kernel (ld_row<S>: 16 B, the tail group 12 / 8 / 4 B); the value buffers hold floats
+// and each value is widened (exactly) as the operand of the fmadd that folds it.  U, keys, nlive, the clamped
+// rows, the gathers, the fold order, the tile buffer and the y writes are those of T.
 #ifndef VBC_LANE_TILE_BYTES
 #define VBC_LANE_TILE_BYTES 8192
 #endif
 constexpr int kLaneTileBytes = VBC_LANE_TILE_BYTES;  // LDS tile buffer per wave (4 workgroups of 4 waves per
                                                      // CU, as the VGPR limit)
 
-template <typename T, int W_, int U, int RUN, bool DEEP, bool RD, int DIAG = 0>
+template <typename T, int W_, int U, int RUN, bool DEEP, bool RD, int DIAG = 0, typename S = T>
 __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int lane, const T *__restrict__ x,
                                                  T *__restrict__ y, T alpha, T beta, T *buf)
 {
@@ -392,7 +397,7 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
     const int s0 = G(b.tseg)[r];
     const int ns = G(b.tseg)[r + 1] - s0;
     int cur = (int)G(b.lseg)[(size_t)r * 64 + lane];  // the lane's current stripe, relative to s0
-    const gptr<const T> val = G(static_cast<const T *>(b.val));
+    const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
     const gptr<const T> xg = G(x);
     const cptr nlive = (cptr)b.nlive;
@@ -404,7 +409,7 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
     int R1v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(R1v) : "s"(R1));
     // fold a step; kk: the runs' keys (or just their PAD / LAST bits)
-    auto compute = [&](int R, const uint32_t (&kk)[NR], const int (&nl)[NR], const T (&v)[U][W_],
+    auto compute = [&](int R, const uint32_t (&kk)[NR], const int (&nl)[NR], const S (&v)[U][W_],
                        const T (&xv)[NR][xrun_slots<T, RUN, true>()]) {
 #pragma unroll
         for (int j = 0; j < NR; j++) {
@@ -417,7 +422,7 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
                 const T xe = kpad ? T(0) : xr[d];
 #pragma unroll
                 for (int e = 0; e < W_; e++) {
-                    const T nv = fmadd(v[j * RUN + d][e], xe, acc[e]);
+                    const T nv = fmadd((T)v[j * RUN + d][e], xe, acc[e]);
                     acc[e] = live ? nv : acc[e];
                 }
             }
@@ -439,13 +444,13 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
             kk[j] = __builtin_nontemporal_load(key + (size_t)Rk * 64 + (lane < nl[j] ? lane : 0));
         }
     };
-    auto load_vals = [&](int R, const int (&nl)[NR], T (&v)[U][W_]) {
+    auto load_vals = [&](int R, const int (&nl)[NR], S (&v)[U][W_]) {
 #pragma unroll
         for (int j = 0; j < NR; j++) {
             const int ln = lane < nl[j] ? lane : 0;
 #pragma unroll
             for (int d = 0; d < RUN; d++)
-                ld_row<T, W_, 0>(val + (size_t)min(R + j * RUN + d, R1 - 1) * 64 * W_, ln, v[j * RUN + d]);
+                ld_row<S, W_, 0>(val + (size_t)min(R + j * RUN + d, R1 - 1) * 64 * W_, ln, v[j * RUN + d]);
         }
     };
     // DIAG (tools/ab.py ablations, VBC_DIAG): 1 = no x gathers (x taken as 1), 2 = gathers confined to
@@ -464,7 +469,8 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
     if constexpr (!DEEP) {
         uint32_t kA[NR], kB[NR];
         int nA[NR], nB[NR];
-        T vA[U][W_], vB[U][W_], xv[NR][xrun_slots<T, RUN, true>()];
+        S vA[U][W_], vB[U][W_];
+        T xv[NR][xrun_slots<T, RUN, true>()];
         load_keys(R0, kA, nA);
         load_vals(R0, nA, vA);
         __builtin_amdgcn_s_waitcnt(0);
@@ -491,7 +497,8 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
         };
         uint32_t kA[NR], kB[NR], fA[NR], fB[NR];
         int nA[NR], nB[NR];
-        T vA[U][W_], vB[U][W_], xA[NR][xrun_slots<T, RUN, true>()], xB[NR][xrun_slots<T, RUN, true>()];
+        S vA[U][W_], vB[U][W_];
+        T xA[NR][xrun_slots<T, RUN, true>()], xB[NR][xrun_slots<T, RUN, true>()];
         load_keys(R0, kA, nA);
         load_keys(R0 + U, kB, nB);
         load_vals(R0, nA, vA);
@@ -547,7 +554,7 @@ __device__ __forceinline__ void run_planar_lanes(const SlotBin &b, int r, int la
     }
 }
 
-template <typename T, int W_, int RUN, bool DEEP, bool RD, int DIAG = 0>
+template <typename T, int W_, int RUN, bool DEEP, bool RD, int DIAG = 0, typename S = T>
 __global__ __launch_bounds__(kBlockThreads) void spmv_planar_lanes(const SlotBin b,
                                                                    const T *__restrict__ x, T *__restrict__ y,
                                                                    T alpha, T beta)
@@ -556,8 +563,8 @@ __global__ __launch_bounds__(kBlockThreads) void spmv_planar_lanes(const SlotBin
     const int rg = __builtin_amdgcn_readfirstlane((int)(blk * kWavesPerBlock + (threadIdx.x >> 6)));
     if (rg >= b.nranges) return;
     __shared__ __attribute__((aligned(16))) T tilebuf[kWavesPerBlock][kLaneTileBytes / sizeof(T)];
-    run_planar_lanes<T, W_, planar_step<T, W_, RUN>(), RUN, DEEP, RD, DIAG>(b, rg, threadIdx.x & 63, x, y, alpha, beta,
-                                                                      tilebuf[threadIdx.x >> 6]);
+    run_planar_lanes<T, W_, planar_step<T, W_, RUN>(), RUN, DEEP, RD, DIAG, S>(b, rg, threadIdx.x & 63, x, y, alpha, beta,
+                                                                         tilebuf[threadIdx.x >> 6]);
 }
 
 // Planar forward product with row runs (SlotBin kind 1, run = R): mul!(y, B, x) for node-blocked rows.

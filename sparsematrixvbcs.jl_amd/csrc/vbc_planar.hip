@@ -13,6 +13,8 @@ int launch_planar_f64n(const SlotBin &hb, bool faste, bool staged, const void *x
 // vbc_pair_f64n.hip: spmv_planar_pair / spmv_pair_lanes <..., float> (lane-pair bins with SlotBin::vsz = 4)
 int launch_pair_f64n(const SlotBin &hb, bool faste, bool staged, const void *x, void *y, double alpha, double beta,
                      bool rd, hipStream_t s);
+// vbc_lanes_f64n.hip: spmv_planar_lanes <double, ..., float> (plain lane-stream bins with SlotBin::vsz = 4)
+int launch_lanes_f64n(const SlotBin &hb, const void *x, void *y, double alpha, double beta, bool rd, hipStream_t s);
 
 template <typename T, int W_, bool KC, int RUN>
 static void launch_w(const SlotBin &hb, const SlotBin *d_b, bool faste, bool staged, const void *x, void *y,
@@ -236,6 +238,8 @@ int launch_planar(int esz, const SlotBin &hb, const SlotBin *d_b, bool faste, bo
                    // lane-pair bins (VBC_CREATE_NARROW_PAIRS): vbc_pair_f64n.hip
         if (esz != 8) return (int)hipErrorInvalidValue;
         if (hb.vsz == 4 && hb.pair) return launch_pair_f64n(hb, faste, staged, x, y, alpha, beta, rd, s);
+        // plain lane streams (VBC_CREATE_NARROW_STREAMS): vbc_lanes_f64n.hip
+        if (hb.vsz == 4 && hb.lanes) return launch_lanes_f64n(hb, x, y, alpha, beta, rd, s);
         return launch_planar_f64n(hb, faste, staged, x, y, alpha, beta, rd, s);
     }
     if (hb.lanes && hb.pair) {  // lane-pair streams (B'x, fp64, w = 3, runs of 3)
