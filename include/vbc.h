@@ -29,7 +29,7 @@
  * bump (vbc_version() still returns 30400, no new symbol): a binding detects the capability by a create with
  * the flag succeeding and by vbc_info.planar_mask bits 12 / 13; a library without it refuses nothing and
  * never sets them.  VBC_CREATE_NARROW_PLANAR likewise: bits 14 / 15; VBC_CREATE_NARROW_PAIRS: bits 16 / 17;
- * VBC_CREATE_NARROW_STREAMS: bits 18 / 19. */
+ * VBC_CREATE_NARROW_STREAMS: bits 18 / 19; VBC_CREATE_NARROW_SWEPT: bits 20 / 21. */
 #define VBC_VERSION 30400
 #define VBC_INFO_SIZE 152
 
@@ -190,8 +190,8 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       operand of the multiply-add that folds it.  As with 0x80 / 0x100 no layout decision
                                       changes and every product is bit-identical to that of the handle created with
                                       0x180 (and so to the wide handle's).  Buckets of spmv_planar_lanes, the split
-                                      and fused-split kernels keep Float64 values; so do the swept, merge and panel /
-                                      tile layouts.  vbc_info.planar_mask bit 16 / 17 say whether a B'x / forward
+                                      and fused-split kernels keep Float64 values; so do the merge and panel / tile
+                                      layouts, and the swept one without VBC_CREATE_NARROW_SWEPT.  vbc_info.planar_mask bit 16 / 17 say whether a B'x / forward
                                       lane-pair bucket stores Float32 (bits 14 / 15 keep meaning the plain planar
                                       buckets); bytes_t, bytes_f and device_bytes count the bytes really stored.
                                       May be combined with VBC_CREATE_NARROW_UPDATABLE.  Refused (VBC_INVALID_ARG, no
@@ -215,8 +215,8 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       0x100 / 0x400 no layout decision changes -- tile size, stream cut, keys and
                                       launch groups are those of the wide handle -- and every product is bit-identical
                                       to that of the handle created with 0x580 (and so to the wide handle's).  The split
-                                      and fused-split kernels keep Float64 values; so do the swept, merge and panel /
-                                      tile layouts.  vbc_info.planar_mask bit 18 / 19 say whether a B'x / forward
+                                      and fused-split kernels keep Float64 values; so do the merge and panel / tile
+                                      layouts, and the swept one without VBC_CREATE_NARROW_SWEPT.  vbc_info.planar_mask bit 18 / 19 say whether a B'x / forward
                                       lane-stream bucket stores Float32 (bits 14 - 17 keep their meaning); bytes_t,
                                       bytes_f and device_bytes count the bytes really stored.  May be combined with
                                       VBC_CREATE_NARROW_UPDATABLE.  Refused (VBC_INVALID_ARG, no device work, no
@@ -226,6 +226,31 @@ typedef enum vbc_mem { VBC_MEM_DEVICE = 0, VBC_MEM_HOST = 1 } vbc_mem;
                                       VBC_CREATE_UPDATABLE_SHARDS).  No version bump and no new symbol, as with 0x80 /
                                       0x100 / 0x400: a binding detects the capability by bits 18 / 19; a library
                                       without it ignores the bit. */
+
+#define VBC_CREATE_NARROW_SWEPT 0x1000u /* Only together with VBC_CREATE_NARROW_VALUES (so on the *_ex creates with
+                                      Float32 values on a Float64 handle); it needs none of 0x100 / 0x400 / 0x800 and
+                                      may be combined with any of them: the handle does everything its other narrow
+                                      bits do and also keeps Float32 values in every bucket create lays out row-swept
+                                      (spmv_sweep) -- B'x (kind 0) and forward (kind 1), packed or unpacked keys, any
+                                      tile size, widths 1..8, from the 1D, 2D or CSC create -- the layout the planner
+                                      picks for inputs without x locality (the reference's own VBR generator).  A
+                                      narrow bucket's value region holds the wide one's steps * 64 * w values as
+                                      floats in the same order: the row of lane l of step s is at float offset
+                                      (s * 64 + l) * w; the region is 16-B aligned and padding slots are zero.  A lane
+                                      widens each value as the operand of the multiply-add that folds it.  As with the
+                                      other narrow bits no layout decision changes -- tiles, steps, keys, S, packing
+                                      and launch shape are those of the handle without the bit -- and every product is
+                                      bit-identical to that handle's (and so to the wide handle's).  The split /
+                                      fused-split, merge and panel / tile layouts keep Float64 values.
+                                      vbc_info.planar_mask bit 20 / 21 say whether a B'x / forward swept bucket stores
+                                      Float32 (bits 12 - 19 keep their meaning); bytes_t, bytes_f and device_bytes
+                                      count the bytes really stored.  May be combined with VBC_CREATE_NARROW_UPDATABLE.
+                                      Refused (VBC_INVALID_ARG, no device work, no handle): 0x1000 without 0x80,
+                                      0x1000 together with VBC_CREATE_UPDATABLE (0x20), and every create that refuses
+                                      0x80 (the creates without vbc_types, any other eltype pair, both sharded creates
+                                      with or without VBC_CREATE_UPDATABLE_SHARDS).  No version bump and no new symbol,
+                                      as with the other narrow bits: a binding detects the capability by bits 20 / 21;
+                                      a library without it ignores the bit. */
 
 /* mul flags */
 #define VBC_MAT_ROWMAJOR 0x2u         /* vbc_mul_mat: X, Y row-major (right-hand sides interleaved,
@@ -515,7 +540,9 @@ typedef struct vbc_info {
                                lane-pair bucket (spmv_planar_pair, spmv_pair_lanes) stores Float32 values
                                (VBC_CREATE_NARROW_PAIRS), bit 17: some forward lane-pair bucket does; bit 18: some
                                B'x lane-stream bucket (spmv_planar_lanes) stores Float32 values
-                               (VBC_CREATE_NARROW_STREAMS), bit 19: some forward lane-stream bucket does */
+                               (VBC_CREATE_NARROW_STREAMS), bit 19: some forward lane-stream bucket does; bit 20: some
+                               B'x row-swept bucket (spmv_sweep) stores Float32 values (VBC_CREATE_NARROW_SWEPT),
+                               bit 21: some forward row-swept bucket does */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

@@ -136,7 +136,8 @@ VBC_API int vbcx_device_facts(int device, vbcx_facts *out);
  * vbc1d_create (pspl = NULL; U, K ignored) or vbc2d_create, checked as those do; dtype = the compute eltype of
  * val; flags = vbc_create_flags without VBC_CREATE_UPDATABLE(_SHARDS) (VBC_CREATE_NARROW_VALUES, alone or with
  * VBC_CREATE_NARROW_PLANAR [| VBC_CREATE_NARROW_PAIRS [| VBC_CREATE_NARROW_STREAMS]]: val holds Float32 values widened
- * to Float64; 0x100 without 0x80, 0x400 without 0x180 and 0x800 without 0x580 are refused;
+ * to Float64; 0x100 without 0x80, 0x400 without 0x180 and 0x800 without 0x580 are refused; VBC_CREATE_NARROW_SWEPT
+ * may join any of them and is refused without 0x80;
  * VBC_CREATE_NARROW_UPDATABLE is accepted together with 0x80 and changes nothing, and is refused without it).  The
  * environment knobs of INTEGRATION.md apply as in a create.  *bytes receives the image size; image = NULL
  * returns only that, else capacity must hold it. */

@@ -25,6 +25,7 @@ VBC_CREATE_NARROW_PLANAR = 0x100  # only together with 0x80: the plain planar bu
 VBC_CREATE_NARROW_UPDATABLE = 0x200  # only together with 0x80 (never with 0x20): the narrow handle plus a value map
 VBC_CREATE_NARROW_PAIRS = 0x400  # only together with 0x80 | 0x100: the lane-pair buckets store Float32 too
 VBC_CREATE_NARROW_STREAMS = 0x800  # only together with 0x80 | 0x100 | 0x400: the plain lane streams store Float32 too
+VBC_CREATE_NARROW_SWEPT = 0x1000  # only together with 0x80 (any of 0x100 / 0x400 / 0x800 or none): the row-swept buckets store Float32 too
 VBC_VERSION_MAJOR = 3 # include/vbc.h VBC_VERSION / 10000: the vbc_info layout below is that version's
 VBC_INFO_SIZE = 152
 VBC_MUL_REFERENCE_QUIRKS = 0x1

@@ -17,6 +17,7 @@ LayoutConfig make_config(int dtype, unsigned flags, unsigned narrow, const Devic
     c.narrow_planar = c.narrow_values && (narrow & VBC_CREATE_NARROW_PLANAR);
     c.narrow_pairs = c.narrow_planar && (narrow & VBC_CREATE_NARROW_PAIRS);
     c.narrow_streams = c.narrow_pairs && (narrow & VBC_CREATE_NARROW_STREAMS);
+    c.narrow_swept = c.narrow_values && (narrow & VBC_CREATE_NARROW_SWEPT);
     if (dtype == VBC_I64) return c;  // the integer layout has no knobs
     const int e32 = c.esz == 4;      // row of the facts
     c.tile_k = dtype == VBC_F64 ? 4 : 8;  // measured best (tools/ab.py, FE workload)

@@ -24,6 +24,8 @@ struct LayoutConfig {
                                   // spmv_planar_pair / spmv_pair_lanes (288 floats per run-row)
     bool narrow_streams = false;  // VBC_CREATE_NARROW_STREAMS (only with narrow_pairs): so do the plain lane-stream bins
                                   // of spmv_planar_lanes, B'x and forward (rows of 64 * w floats)
+    bool narrow_swept = false;    // VBC_CREATE_NARROW_SWEPT (only with narrow_values, whatever the bits between): so do
+                                  // the row-swept bins of spmv_sweep, B'x and forward (rows of w floats per lane slot)
     int target_ranges_m = 4096;
     int panel_valu = 0;           // ablation bits of the panel kernel (VBC_PANEL_VALU / VBC_PANEL_DIAG, the VBC_ABLATION
                                   // build only; 0 in the product library)
@@ -119,8 +121,8 @@ struct LayoutConfig {
 
 // The whole environment block of a create.  `flags`: vbc_create_flags (VBC_CREATE_SERIAL overrides two knobs, the
 // MULTI flags enable the panel / tile knobs).  `narrow`: the narrow-storage bits the create accepted
-// (VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR, VBC_CREATE_NARROW_PAIRS, VBC_CREATE_NARROW_STREAMS; 0: none) --
-// they are not part of `flags`.
+// (VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR, VBC_CREATE_NARROW_PAIRS, VBC_CREATE_NARROW_STREAMS,
+// VBC_CREATE_NARROW_SWEPT; 0: none) -- they are not part of `flags`.
 LayoutConfig make_config(int dtype, unsigned flags, unsigned narrow, const DeviceFacts &facts);
 
 }  // namespace vbc

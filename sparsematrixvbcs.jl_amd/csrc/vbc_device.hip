@@ -1190,7 +1190,13 @@ static int build_sweep(PlanCtx *h, int kind, int w, const std::vector<int64_t> &
     pw.o_key = ar.reserve(E * 4);
     pw.o_loc = ar.reserve(packed ? 4 : E * 2);
     pw.o_sbase = ar.reserve(packed ? (size_t)nsteps * 4 : 4);
-    pw.o_val = ar.reserve(E * w * esz);
+    // VBC_CREATE_NARROW_SWEPT: the value rows store floats, row e at float offset e * w (an arena reservation, so
+    // 16-B aligned); everything above -- S, the steps, the keys, packing -- was decided with esz.
+    const bool narrow = esz == 8 && h->narrow_swept;
+    const int vsz = narrow ? 4 : esz;
+    b.vsz = narrow ? 4 : 0;
+    pw.o_val = ar.reserve(E * w * vsz);
+    if (narrow && h->rec) h->rec->narrow.emplace_back(pw.o_val, pw.o_val + (size_t)E * w * vsz);
     pw.o_out = ar.reserve(out.size() * 4);
     std::memcpy(ar.at<int32_t>(pw.o_tstep), tstep.data(), tstep.size() * 4);
     std::memcpy(ar.at<uint32_t>(pw.o_key), keys.data(), E * 4);
@@ -1199,11 +1205,14 @@ static int build_sweep(PlanCtx *h, int kind, int w, const std::vector<int64_t> &
     std::memcpy(ar.at<int32_t>(pw.o_out), out.data(), out.size() * 4);
     char *vv = ar.at<char>(pw.o_val);
     for (int64_t e = 0; e < E; e++) {
-        if (voffs[e] >= 0) std::memcpy(vv + e * w * esz, val + voffs[e] * esz, (size_t)w * esz);
-        else std::memset(vv + e * w * esz, 0, (size_t)w * esz);
+        if (voffs[e] < 0) std::memset(vv + e * w * vsz, 0, (size_t)w * vsz);
+        else if (narrow)
+            for (int cc = 0; cc < w; cc++)
+                narrow_value(h, reinterpret_cast<const double *>(val) + voffs[e] + cc, vv + (e * w + cc) * 4);
+        else std::memcpy(vv + e * w * esz, val + voffs[e] * esz, (size_t)w * esz);
     }
     (kind == 0 ? h->st.bytes_t : h->st.bytes_f) +=
-        E * ((packed ? 4 : 6) + (int64_t)w * esz) + (packed ? nsteps * 4 : 0) + (int64_t)tstep.size() * 4 +
+        E * ((packed ? 4 : 6) + (int64_t)w * vsz) + (packed ? nsteps * 4 : 0) + (int64_t)tstep.size() * 4 +
         (b.out_affine ? 0 : nseg * 4);
     return VBC_OK;
 }
@@ -3041,6 +3050,7 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
             cfg_c.narrow_planar = cfg.narrow_planar && cfg_c.narrow_values;
             cfg_c.narrow_pairs = cfg.narrow_pairs && cfg_c.narrow_planar;
             cfg_c.narrow_streams = cfg.narrow_streams && cfg_c.narrow_pairs;
+            cfg_c.narrow_swept = cfg.narrow_swept && cfg_c.narrow_values;
             h->st.ft_narrow = cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
             st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
@@ -3311,7 +3321,11 @@ static int refuse_narrow_flag(vbc_handle **out, const char *why)
     return fail(VBC_INVALID_ARG, why);
 }
 constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS |
-                                 VBC_CREATE_NARROW_STREAMS;
+                                 VBC_CREATE_NARROW_STREAMS | VBC_CREATE_NARROW_SWEPT;
+constexpr const char *kNarrowSweptAlone = "VBC_CREATE_NARROW_SWEPT is valid only together with VBC_CREATE_NARROW_VALUES";
+constexpr const char *kNarrowSweptPlain = "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs Float32 values on a "
+                                          "Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
+                                          "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
 constexpr unsigned kNarrowBelowStreams = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS;
 constexpr const char *kNarrowStreamsAlone = "VBC_CREATE_NARROW_STREAMS is valid only together with VBC_CREATE_NARROW_VALUES, "
                                             "VBC_CREATE_NARROW_PLANAR and VBC_CREATE_NARROW_PAIRS";
@@ -3385,6 +3399,7 @@ static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t 
                      int64_t nval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
     if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
@@ -3473,6 +3488,7 @@ static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t 
                      int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
     if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
@@ -3579,6 +3595,7 @@ static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *col
                       const void *nzval, int dtype, int device, unsigned flags, unsigned narrow)
 {
     if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
+    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
     if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
     if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
     if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
@@ -3611,6 +3628,9 @@ int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const
         return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
     flags &= ~VBC_CREATE_NARROW_UPDATABLE;  // (it changes no layout)
     const unsigned narrow = flags & kNarrowBits;
+    if ((narrow & VBC_CREATE_NARROW_SWEPT) && !(narrow & VBC_CREATE_NARROW_VALUES)) return fail(VBC_INVALID_ARG, kNarrowSweptAlone);
+    if ((narrow & VBC_CREATE_NARROW_SWEPT) && dtype != VBC_F64)
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs a Float64 handle");
     if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
         return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
@@ -3650,6 +3670,9 @@ int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const 
     if (int st = stripes(nullptr, in, sv)) return st;
     flags &= ~(VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS | VBC_CREATE_NARROW_UPDATABLE);
     const unsigned narrow = flags & kNarrowBits;
+    if ((narrow & VBC_CREATE_NARROW_SWEPT) && !(narrow & VBC_CREATE_NARROW_VALUES)) return fail(VBC_INVALID_ARG, kNarrowSweptAlone);
+    if ((narrow & VBC_CREATE_NARROW_SWEPT) && dtype != VBC_F64)
+        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs a Float64 handle");
     if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
         return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
     if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
@@ -3773,6 +3796,16 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     if (h->has_ft)
         for (const SlotBin &b : h->lft.pbins)
             if (b.vsz) info->planar_mask |= 1 << narrow_bit(b, true);
+    if (h->has_t)
+        for (const SweepBin &b : h->lt.wbins)
+            if (b.vsz) info->planar_mask |= 1 << 20;  // B'x row-swept buckets of Float32 values (VBC_CREATE_NARROW_SWEPT)
+    if (h->has_f)
+        for (const auto &l : h->lf)
+            for (const SweepBin &b : l.wbins)
+                if (b.vsz) info->planar_mask |= 1 << 21;  // forward ones
+    if (h->has_ft)
+        for (const SweepBin &b : h->lft.wbins)
+            if (b.vsz) info->planar_mask |= 1 << 21;
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -4011,6 +4044,16 @@ static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, u
     narrow = 0;
     const bool upd = (flags & VBC_CREATE_NARROW_UPDATABLE) != 0;  // (its refusals name it)
     if (!(flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE))) return VBC_OK;
+    if (flags & VBC_CREATE_NARROW_SWEPT) {  // (its refusals name it, whatever else is set)
+        if (!(flags & VBC_CREATE_NARROW_VALUES)) return refuse_narrow_flag(out, kNarrowSweptAlone);
+        if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
+            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs val_dtype VBC_F32 "
+                                           "and compute_dtype VBC_F64");
+        if (flags & VBC_CREATE_UPDATABLE)
+            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) cannot be combined with "
+                                           "VBC_CREATE_UPDATABLE: a narrow handle is made updatable by "
+                                           "VBC_CREATE_NARROW_UPDATABLE instead");
+    }
     if (flags & VBC_CREATE_NARROW_STREAMS) {  // (its refusals name it too, whatever else is set)
         if ((flags & kNarrowBelowStreams) != kNarrowBelowStreams) return refuse_narrow_flag(out, kNarrowStreamsAlone);
         if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)

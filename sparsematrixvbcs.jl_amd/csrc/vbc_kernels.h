@@ -197,7 +197,8 @@ constexpr int64_t kSlotIdxLimit = int64_t(1) << 30;  // gather indices of the sl
 // back and the gathers of the concurrently resident waves fall into a narrow window of x.
 struct SweepBin {
     int32_t kind;        // 0: B'x (segment = stripe, w outputs), 1: Bx (segment = output row)
-    int32_t pad_;
+    int32_t vsz;         // 4: the values are Float32 on an fp64 bin (VBC_CREATE_NARROW_SWEPT; every swept bin of the
+                         // handle alike); 0 = values of the compute eltype
     int32_t w;           // entry width (1..8)
     int32_t tile0;       // first tile (wave) of this bucket in the launch
     int32_t ntiles;
@@ -212,14 +213,15 @@ struct SweepBin {
     const uint32_t *key;   // steps * 64: PAD | gather index (B'x: x row; Bx: first x column), or packed
     const uint16_t *loc;   // steps * 64: segment within the tile (not packed)
     const uint32_t *sbase; // packed: steps: the step's smallest gather index (its first lane's)
-    const void *val;       // steps * 64 * w values
+    const void *val;       // steps * 64 * w values (floats when vsz = 4), lane l of step s at (s * 64 + l) * w
     const int32_t *out;    // per stripe: first y column (when not affine)
 };
 constexpr int kSweepTileBytes = 8192;  // LDS accumulators per wave: VBC_SWEEP_TILE = 8 / 16 / 32 (KB)
 
 // Launches spmv_sweep (vbc_sweep.hip): returns the hipError_t of the launch.
-int launch_sweep(int esz, int kind, const SweepBin *d_bins, int nbins, int total_tiles, int tile_bytes, int diag, const void *x,
-                 void *y, double alpha, double beta, bool rd, hipStream_t stream);
+// vsz: size of the stored values (esz, or 4 on an fp64 launch whose bins all keep Float32 values).
+int launch_sweep(int esz, int vsz, int kind, const SweepBin *d_bins, int nbins, int total_tiles, int tile_bytes, int diag,
+                 const void *x, void *y, double alpha, double beta, bool rd, hipStream_t stream);
 
 constexpr int kWonlyNarrow2 = 102;  // spmv_slots WONLY: fp32 B'x w = 2 folded two segments per lane (run_slots_narrow)
 // Launches spmv_slots (vbc_slots.hip): returns the hipError_t of the launch.

@@ -32,8 +32,13 @@ static int launch_group(const Launch &L, int kind, const void *x, void *y, doubl
         return g < 0 || gi++ == g;
     };
     if (mine(L.sweep_tiles > 0)) {
-        const hipError_t e = (hipError_t)launch_sweep((int)sizeof(T), kind, L.d_wbins, (int)L.wbins.size(), L.sweep_tiles,
-                                                      L.sweep_tile_bytes, L.sweep_diag, x, y, alpha, beta, rd, stream);
+        // VBC_CREATE_NARROW_SWEPT: every swept bin of the launch stores Float32 values, or none does
+        const int vsz0 = L.wbins.empty() ? 0 : L.wbins[0].vsz;
+        for (const SweepBin &wb : L.wbins)
+            if (wb.vsz != vsz0) return fail(VBC_INVALID_ARG, "internal: swept bins of one launch store different value types");
+        const hipError_t e = (hipError_t)launch_sweep((int)sizeof(T), vsz0 > 0 ? vsz0 : (int)sizeof(T), kind, L.d_wbins,
+                                                      (int)L.wbins.size(), L.sweep_tiles, L.sweep_tile_bytes,
+                                                      L.sweep_diag, x, y, alpha, beta, rd, stream);
         if (e != hipSuccess) {
             set_error("spmv_sweep launch failed: %s", hipGetErrorString(e));
             return VBC_HIP_ERROR;

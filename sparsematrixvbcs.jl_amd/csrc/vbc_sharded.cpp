@@ -692,6 +692,9 @@ int create_sharded(vbc_sharded **out, Fields &f, int64_t nval, const vbc_types *
     *out = nullptr;
     if (!types) return vbc::fail(VBC_INVALID_ARG, "NULL vbc_types");
     if (ngpus < 1 || !devices) return vbc::fail(VBC_INVALID_ARG, "ngpus must be >= 1 with a device list");
+    if (flags & VBC_CREATE_NARROW_SWEPT)
+        return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) is not supported on "
+                                          "sharded handles");
     if (flags & VBC_CREATE_NARROW_STREAMS)
         return vbc::fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES) is not supported on "
                                           "sharded handles");

@@ -89,7 +89,8 @@ Device-resident copies of `B`, one libvbc handle per compute eltype met (created
 device (slotted buckets; same bits as without); `narrow=:planar` (VBC_CREATE_NARROW_VALUES |
 VBC_CREATE_NARROW_PLANAR) also in the planar buckets of the plain planar kernels, `narrow=:pairs` (adds
 VBC_CREATE_NARROW_PAIRS) also in those of the lane-pair kernels, `narrow=:streams` (adds
-VBC_CREATE_NARROW_STREAMS) also in the lane streams of `spmv_planar_lanes`.  For any other eltype pair the
+VBC_CREATE_NARROW_STREAMS) also in the lane streams of `spmv_planar_lanes`, `narrow=:swept` (adds
+VBC_CREATE_NARROW_SWEPT) also in the row-swept buckets of `spmv_sweep`.  For any other eltype pair the
 keyword is ignored; any other value, or `narrow` and `updatable` together, throw an ArgumentError.
 """
 mutable struct HIPSparseMatrix1DVBC{W, Tv, Ti}
@@ -187,7 +188,7 @@ function handle_for(A::HIPMatrix, ::Type{Ty}) where {Ty}
     # narrow values: only Float32 values on a Float64 handle (the library refuses the flag for any other pair)
     flags = (eltype(A) === Float32 && cdt == VBC_F64) ? A.flags :
             A.flags & ~(VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS |
-                        VBC_CREATE_NARROW_STREAMS)
+                        VBC_CREATE_NARROW_STREAMS | VBC_CREATE_NARROW_SWEPT)
     get!(() -> _create(A.host, A.device, flags, cdt), A.handles, cdt)
 end
 
@@ -284,18 +285,21 @@ const VBC_CREATE_NARROW_VALUES = Cuint(0x80)  # Float32 values kept narrow on a 
 const VBC_CREATE_NARROW_PLANAR = Cuint(0x100)  # only with 0x80: the plain planar buckets too
 const VBC_CREATE_NARROW_PAIRS = Cuint(0x400)  # only with 0x80 | 0x100: the lane-pair buckets too
 const VBC_CREATE_NARROW_STREAMS = Cuint(0x800)  # only with 0x80 | 0x100 | 0x400: the plain lane streams too
+const VBC_CREATE_NARROW_SWEPT = Cuint(0x1000)  # only with 0x80 (any of 0x100 / 0x400 / 0x800 or none): the row-swept buckets too
 
 # the `narrow` keyword of the single-GPU constructors: false, true (0x80), :planar (0x80 | 0x100),
-# :pairs (0x80 | 0x100 | 0x400) or :streams (0x80 | 0x100 | 0x400 | 0x800)
+# :pairs (0x80 | 0x100 | 0x400), :streams (0x80 | 0x100 | 0x400 | 0x800) or :swept (all of those | 0x1000)
 function narrow_flags(narrow, updatable::Bool)
     narrow === false && return Cuint(0)
-    narrow === true || narrow === :planar || narrow === :pairs || narrow === :streams ||
-        throw(ArgumentError("narrow must be false, true, :planar, :pairs or :streams"))
+    narrow === true || narrow === :planar || narrow === :pairs || narrow === :streams || narrow === :swept ||
+        throw(ArgumentError("narrow must be false, true, :planar, :pairs, :streams or :swept"))
     updatable && throw(ArgumentError("narrow and updatable cannot be combined"))
     narrow === true && return VBC_CREATE_NARROW_VALUES
     narrow === :planar && return VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR
     narrow === :pairs && return VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS
-    return VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS | VBC_CREATE_NARROW_STREAMS
+    streams = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS | VBC_CREATE_NARROW_STREAMS
+    narrow === :streams && return streams
+    return streams | VBC_CREATE_NARROW_SWEPT
 end
 const VBC_CREATE_UPDATABLE_SHARDS = Cuint(0x40)  # the sharded creates only (they refuse 0x20)
 

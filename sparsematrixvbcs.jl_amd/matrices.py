@@ -83,7 +83,9 @@ class _DeviceMatrix:
         (vbc.h VBC_CREATE_NARROW_PLANAR, passed together with 0x80); `B.narrow = "pairs"` also in the buckets of
         the lane-pair kernels (vbc.h VBC_CREATE_NARROW_PAIRS, passed together with 0x80 | 0x100);
         `B.narrow = "streams"` also in the lane streams of spmv_planar_lanes (vbc.h VBC_CREATE_NARROW_STREAMS,
-        passed together with 0x80 | 0x100 | 0x400); any other value raises ValueError.
+        passed together with 0x80 | 0x100 | 0x400); `B.narrow = "swept"`, the top of the ladder, also in the row-swept
+        buckets of spmv_sweep (vbc.h VBC_CREATE_NARROW_SWEPT, passed together with all of the above: 0x1D80); any other
+        value raises ValueError.
         `B.updatable` is False, True (vbc.h VBC_CREATE_UPDATABLE) or "narrow": updatable, and where narrow
         storage is in effect (`B.narrow` set, a float32 matrix, Float64 compute) the handle is created with
         VBC_CREATE_NARROW_UPDATABLE instead of 0x20 and update_values takes float32 values only; where `B.narrow`
@@ -108,20 +110,22 @@ class _DeviceMatrix:
             flags |= _L.VBC_CREATE_UPDATABLE  # update_values rewrites the stored values in place
         narrow = getattr(self, "narrow", False)
         if not (narrow is False or narrow is None or narrow is True
-                or (isinstance(narrow, str) and narrow in ("planar", "pairs", "streams"))):
-            raise ValueError("B.narrow must be False, True, 'planar', 'pairs' or 'streams', not %r" % (narrow,))
+                or (isinstance(narrow, str) and narrow in ("planar", "pairs", "streams", "swept"))):
+            raise ValueError("B.narrow must be False, True, 'planar', 'pairs', 'streams' or 'swept', not %r" % (narrow,))
         if narrow:
             if updatable is True:
                 raise _L.ArgumentError("B.narrow and B.updatable = True cannot be combined (that update writes values "
                                        "of the compute eltype): set B.updatable = 'narrow'")
             if not multi and self._val.dtype == np.float32 and compute == _L.VBC_F64:
                 flags |= _L.VBC_CREATE_NARROW_VALUES  # Float32 values in HBM, widened in registers
-                if narrow is not True:  # "planar" / "pairs" / "streams"
+                if narrow is not True:  # "planar" / "pairs" / "streams" / "swept"
                     flags |= _L.VBC_CREATE_NARROW_PLANAR  # the plain planar buckets too
-                if narrow in ("pairs", "streams"):
+                if narrow in ("pairs", "streams", "swept"):
                     flags |= _L.VBC_CREATE_NARROW_PAIRS  # and the lane-pair buckets
-                if narrow == "streams":
+                if narrow in ("streams", "swept"):
                     flags |= _L.VBC_CREATE_NARROW_STREAMS  # and the plain lane streams
+                if narrow == "swept":
+                    flags |= _L.VBC_CREATE_NARROW_SWEPT  # and the row-swept buckets
                 if updatable:  # "narrow": the narrow handle plus a value map; its updates take float32 values only
                     flags = (flags & ~_L.VBC_CREATE_UPDATABLE) | _L.VBC_CREATE_NARROW_UPDATABLE
         return self._handles.get((int(device), flags, compute),
@@ -146,6 +150,9 @@ class _DeviceMatrix:
         # bits 18 / 19: a B'x / forward lane-stream bucket does (VBC_CREATE_NARROW_STREAMS)
         d["narrow_streams_t"] = bool(inf.planar_mask & (1 << 18))
         d["narrow_streams_f"] = bool(inf.planar_mask & (1 << 19))
+        # bits 20 / 21: a B'x / forward row-swept bucket does (VBC_CREATE_NARROW_SWEPT)
+        d["narrow_swept_t"] = bool(inf.planar_mask & (1 << 20))
+        d["narrow_swept_f"] = bool(inf.planar_mask & (1 << 21))
         return d
 
     def release(self):
