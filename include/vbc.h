@@ -373,8 +373,16 @@ VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int
  * mul! (Base.:* forwards to an undefined method, multiply_1DVBC.jl:184-185), so the semantics is
  * defined column by column as vbc_mul.  trans = 1 on a handle with VBC_CREATE_MULTI: one
  * matrix-core pass per 64 right-hand sides, row- or column-major.  Otherwise the transposed
- * row-major product with widths <= 8 runs a fused vector kernel over the SpMV layout, and the other
- * cases run one SpMV per column. */
+ * row-major product of a float handle runs fused vector kernels over the B'x (SpMV) layout when that
+ * layout consists of
+ *   - merge buckets of widths <= 8 (spmm_ranges: the matrix read once per 64 right-hand sides), and
+ *   - slotted buckets of widths <= 8 (spmm_slots, from nrhs = 2 on: the matrix read once per 8
+ *     right-hand sides, every column bit-identical to vbc_mul of that column; Float32-stored buckets
+ *     of VBC_CREATE_NARROW_VALUES and updatable handles included; vbc_info.planar_mask bit 22).
+ * A layout with a planar or a row-swept bucket or a bucket wider than 8, an integer handle,
+ * column-major operands, the forward direction, nrhs = 1 on a slotted layout and a handle created under
+ * the layout knob VBC_MM_SLOTS=0 (slotted layouts only; clears bit 22) run one SpMV per column, the
+ * row-major ones through two or three strided copies per column. */
 VBC_API int vbc_mul_mat(vbc_handle *h, int trans, int64_t nrhs, const void *X, int64_t ldx, int64_t nx,
                 void *Y, int64_t ldy, int64_t ny, double alpha, double beta, int mem, void *stream,
                 unsigned flags);
@@ -542,7 +550,10 @@ typedef struct vbc_info {
                                B'x lane-stream bucket (spmv_planar_lanes) stores Float32 values
                                (VBC_CREATE_NARROW_STREAMS), bit 19: some forward lane-stream bucket does; bit 20: some
                                B'x row-swept bucket (spmv_sweep) stores Float32 values (VBC_CREATE_NARROW_SWEPT),
-                               bit 21: some forward row-swept bucket does */
+                               bit 21: some forward row-swept bucket does; bit 22: the B'x layout has a
+                               slotted bucket and the row-major transposed vbc_mul_mat of this handle runs fused
+                               over it (spmm_slots: the matrix read once per 8 right-hand sides); decided at
+                               create, clear under VBC_MM_SLOTS=0 and for the layouts vbc_mul_mat lists */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

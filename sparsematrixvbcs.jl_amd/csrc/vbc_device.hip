@@ -3806,6 +3806,9 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     if (h->has_ft)
         for (const SweepBin &b : h->lft.wbins)
             if (b.vsz) info->planar_mask |= 1 << 21;
+    bool mm_slotted = false;
+    if (mulmat_fuses(h, &mm_slotted) && mm_slotted)
+        info->planar_mask |= 1 << 22;  // row-major B'X runs fused over the slotted buckets (spmm_slots)
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3936,9 +3939,10 @@ static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX
 {
     const int64_t esz = h->esz;
     int st = VBC_OK;
-    bool fused = rowmajor && trans && nrhs > 0 && h->n > 0 && h->has_t && h->dtype != VBC_I64;
-    for (const Bin &b : h->lt.bins) fused = fused && b.wkey != 0;  // runtime-width buckets: per column
-    fused = fused && h->lt.sbins.empty() && h->lt.wbins.empty() && h->lt.pbins.empty();  // the fused vector kernel reads the merge layout only
+    // the fused vector kernels read the merge layout and, from kMmSlotsMinRhs columns on, the slotted one
+    bool slotted = false;
+    bool fused = rowmajor && trans && nrhs > 0 && mulmat_fuses(h, &slotted);
+    if (slotted && nrhs < kMmSlotsMinRhs) fused = false;
     if (trans ? (h->has_m && nrhs > 0 && h->n > 0) : (h->has_mf && nrhs > 0 && h->m > 0)) {  // matrix-core panels
         const int64_t sxr = rowmajor ? ldx : 1, sxc = rowmajor ? 1 : ldx;
         const int64_t syr = rowmajor ? ldy : 1, syc = rowmajor ? 1 : ldy;

@@ -180,6 +180,11 @@ namespace vbc {
 int launch_groups(const Launch &L);  // independent launch groups of a B'x launch (vbc_launch.hip)
 int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double alpha, double beta,
                  hipStream_t stream);
+// Row-major B'X with nrhs >= kMmSlotsMinRhs columns runs fused over the handle's B'x layout (mulmat_rowmajor): merge
+// bins of compile-time widths, and slotted bins through spmm_slots unless VBC_MM_SLOTS=0.  The one predicate of the
+// dispatch (vbc_mul_mat) and of vbc_info.planar_mask bit 22 (*slotted: the layout has a slotted bucket).
+bool mulmat_fuses(const vbc_handle *h, bool *slotted);
+constexpr int64_t kMmSlotsMinRhs = 2;  // smallest nrhs the slotted part runs fused at (profiles/mm_slots_time.json)
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
 void occupancy_ranges(int esz, int K, int P, int occ[2]);

@@ -1,5 +1,5 @@
 // libvbc kernel launches of the vector products: merge kernel (vbc_kernels.h) + slotted kernel
-// (vbc_slots.hip), their fix-up passes, and the fused vector multi-RHS kernel.
+// (vbc_slots.hip), their fix-up passes, and the fused vector multi-RHS kernels (spmm_ranges, spmm_slots).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -248,17 +248,73 @@ int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double 
                                : mul_device<float>(h, trans, x, y, alpha, beta, stream);
 }
 
+int launch_slots_mm_f64(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
+                        int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
+int launch_slots_mm_f32(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
+                        int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
+int launch_slots_mm_f64n(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
+                         int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
+
+bool mulmat_fuses(const vbc_handle *h, bool *slotted)
+{
+    const Launch &L = h->lt;
+    if (slotted) *slotted = h->has_t && !L.sbins.empty();
+    if (!h->has_t || h->n <= 0 || h->dtype == VBC_I64) return false;
+    if (!L.wbins.empty() || !L.pbins.empty()) return false;  // planar and swept buckets: per column
+    for (const Bin &b : L.bins)
+        if (b.wkey == 0) return false;  // runtime-width buckets: per column
+    if (L.sbins.empty()) return true;   // the merge layout alone: spmm_ranges, as ever
+    if (!h->cfg.mm_slots) return false;
+    const SlotBin &f = L.sbins[0];
+    if (f.vsz != 0 && !(f.vsz == 4 && h->esz == 8)) return false;
+    for (const SlotBin &b : L.sbins) {
+        // the forms spmm_slots covers: kind 0, a compile-time width, one segment per lane slot or the fp32 w = 2
+        // two-segment rows; keys and stored value type alike in every bin of the launch
+        const bool narrow2 = h->esz == 4 && b.spl == 2 && b.wkey == 2;
+        if (b.kind != 0 || b.planar || b.wkey < 1 || b.wkey > 8 || !(b.spl == 1 || narrow2)) return false;
+        if (b.vsz != f.vsz || (b.kc != 0) != (f.kc != 0) || VBC_ABL(b.diag != 0)) return false;
+    }
+    return true;
+}
+
+// The slotted bins of a row-major B'X (spmm_slots, vbc_slots_mm.h): chunks of <= 8 columns one after another on
+// the caller's stream, nothing allocated.
+static int mulmat_slots(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
+                        double alpha, double beta, hipStream_t s)
+{
+    const Launch &L = h->lt;
+    int wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
+    for (const SlotBin &b : L.sbins)
+        if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
+    const int vsz = L.sbins[0].vsz > 0 ? L.sbins[0].vsz : h->esz;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 8) {
+        const int nr = (int)std::min<int64_t>(8, nrhs - c0);
+        const char *xs = X + c0 * h->esz;
+        char *ys = Y + c0 * h->esz;
+        const auto fn = h->esz == 4 ? launch_slots_mm_f32 : vsz == 4 ? launch_slots_mm_f64n : launch_slots_mm_f64;
+        const hipError_t e = (hipError_t)fn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, L.sbins[0].kc != 0,
+                                            wonly, xs, ldx, ys, ldy, nr, alpha, beta, beta != 0.0, s);
+        if (e != hipSuccess) {
+            set_error("spmm_slots launch failed: %s", hipGetErrorString(e));
+            return VBC_HIP_ERROR;
+        }
+    }
+    return VBC_OK;
+}
+
 // Multi-RHS transposed product on the tiled stream (row-major X / Y), in chunks of <= 64 columns.
 template <typename T>
 static int mulmat_t_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
                              double alpha, double beta, hipStream_t s)
 {
     const Launch &L = h->lt;
+    if (L.slot_ranges > 0)  // the slotted bins (their own stripes of y) first, as launch_group orders them
+        if (int st = mulmat_slots(h, nrhs, X, ldx, Y, ldy, alpha, beta, s)) return st;
     const int NRmax = 64;
     int64_t stride = 1;
     for (const Bin &b : L.bins) stride = std::max<int64_t>(stride, (int64_t)b.nranges * b.w * NRmax);
     const size_t need = (size_t)std::max<size_t>(L.bins.size(), 1) * stride * sizeof(T);
-    if (h->carry_mm_bytes < need) {
+    if (!L.bins.empty() && h->carry_mm_bytes < need) {  // (carry slots of the merge bins only)
         if (h->d_carry_mm) (void)hipFree(h->d_carry_mm);
         h->d_carry_mm = nullptr;
         h->carry_mm_bytes = 0;

@@ -1,0 +1,4 @@
+// spmm_slots launchers, fp64.
+#define VBC_SLOTS_T double
+#define VBC_SLOTS_SUFFIX f64
+#include "vbc_slots_mm_launch.inc"
