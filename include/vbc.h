@@ -363,6 +363,10 @@ VBC_API int vbc_mul(vbc_handle *h, int trans, const void *x, int64_t nx, void *y
  * on an integer handle.  incx / incy: element strides (any nonzero value; negative = reversed view,
  * the pointer is that of x[1] / y[1]).  Contiguous operands of the compute eltype go straight to the
  * kernels; others through the handle's staging buffers (a conversion kernel on each side).
+ * The staging buffers are allocated by the first such product of the handle (and when a later one needs
+ * them larger): on a capturing `stream` that product returns VBC_INVALID_ARG before it allocates anything
+ * and the capture stays valid, so run the product once outside the capture before capturing it.
+ * Products of one handle that use the staging buffers are ordered after one another whatever their streams.
  * mem, stream, flags as vbc_mul. */
 VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int64_t incx, int64_t nx, void *y,
                        int y_dtype, int64_t incy, int64_t ny, double alpha, double beta, int mem, void *stream,
@@ -382,7 +386,13 @@ VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int
  * A layout with a planar or a row-swept bucket or a bucket wider than 8, an integer handle,
  * column-major operands, the forward direction, nrhs = 1 on a slotted layout and a handle created under
  * the layout knob VBC_MM_SLOTS=0 (slotted layouts only; clears bit 22) run one SpMV per column, the
- * row-major ones through two or three strided copies per column. */
+ * row-major ones through two or three strided copies per column.
+ * The column temporaries of that row-major per-column path and the carry buffer of spmm_ranges are
+ * allocated by the handle's first product on the path: on a capturing `stream` that product returns
+ * VBC_INVALID_ARG before it allocates anything and the capture stays valid, so run the product once
+ * outside the capture before capturing it.  The panel products share no buffer and are never ordered
+ * against one another; products that share one (host operands, the column temporaries, the merge
+ * layout's carries) are ordered after one another whatever their streams. */
 VBC_API int vbc_mul_mat(vbc_handle *h, int trans, int64_t nrhs, const void *X, int64_t ldx, int64_t nx,
                 void *Y, int64_t ldy, int64_t ny, double alpha, double beta, int mem, void *stream,
                 unsigned flags);

@@ -3843,7 +3843,7 @@ struct ProductOrder {
     vbc_handle *h;
     hipStream_t s;
     bool active = false;
-    bool force = false;  // the product uses the handle's staging buffers on the device path
+    bool force = false;  // the call uses the handle's staging buffers (host operands or staged device ones)
     ProductOrder(vbc_handle *h_, hipStream_t s_, bool force_ = false) : h(h_), s(s_), force(force_) {}
     int begin()
     {
@@ -3866,12 +3866,14 @@ struct ProductOrder {
     }
 };
 
-// Cached device staging buffer `which` (0: x / X, 1: y / Y) of at least `bytes` (caller holds h->mu).
-static int stage_buffer(vbc_handle *h, int which, size_t bytes, void **out)
+// Cached device staging buffer `which` (0: x / X, 1: y / Y; 2, 3: column temporaries) of at least `bytes` for a
+// product on `s` (caller holds h->mu).  Growing it is refused while `s` is capturing (may_grow).
+static int stage_buffer(vbc_handle *h, int which, size_t bytes, hipStream_t s, void **out)
 {
     bytes = std::max<size_t>(bytes, 256);
     if (h->stage_bytes[which] < bytes) {
-        // every host-pointer call synchronises its stream before returning: the old buffer is idle
+        if (int st = may_grow(s, "a staging buffer")) return st;
+        // hipFree waits for the device: a product still using the old buffer on another stream has finished
         const size_t grow = std::max(bytes, h->stage_bytes[which] + h->stage_bytes[which] / 2);
         if (h->d_stage[which]) (void)hipFree(h->d_stage[which]);
         h->d_stage[which] = nullptr;
@@ -3909,9 +3911,9 @@ int vbc_mul(vbc_handle *h, int trans, const void *x, int64_t nx, void *y, int64_
     // Host pointers: stage through the handle's cached device buffers (no per-call allocation).
     std::lock_guard<std::mutex> lk(h->mu);
     void *dx = nullptr, *dy = nullptr;
-    if (int st = stage_buffer(h, 0, nx * esz, &dx)) return st;
-    if (int st = stage_buffer(h, 1, ny * esz, &dy)) return st;
-    ProductOrder po(h, s);
+    if (int st = stage_buffer(h, 0, nx * esz, s, &dx)) return st;
+    if (int st = stage_buffer(h, 1, ny * esz, s, &dy)) return st;
+    ProductOrder po(h, s, true);  // a staged product on another stream may be using the same two buffers
     if (int st = po.begin()) return st;
     if (nx > 0 && hipMemcpyAsync(dx, x, nx * esz, hipMemcpyHostToDevice, s) != hipSuccess)
         return fail(VBC_HIP_ERROR, "staging copy of x failed");
@@ -3933,23 +3935,34 @@ static bool copy2d(void *dst, size_t dpitch, const void *src, size_t spitch, siz
     return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, s) == hipSuccess;
 }
 
+// The path of a multi-RHS product on device operands: the one dispatch of mul_mat_device, and what vbc_mul_mat
+// orders (only kMatColumnTemps touches the handle's staging buffers; kMatFused's carries set has_scratch).
+enum MatPath { kMatPanels, kMatFused, kMatColumns, kMatColumnTemps };
+static MatPath mat_path(const vbc_handle *h, int trans, int64_t nrhs, bool rowmajor)
+{
+    if (trans ? (h->has_m && nrhs > 0 && h->n > 0) : (h->has_mf && nrhs > 0 && h->m > 0)) return kMatPanels;
+    // the fused vector kernels read the merge layout and, from kMmSlotsMinRhs columns on, the slotted one
+    bool slotted = false;
+    bool fused = rowmajor && trans && nrhs > 0 && mulmat_fuses(h, &slotted);
+    if (slotted && nrhs < kMmSlotsMinRhs) fused = false;
+    if (fused) return kMatFused;
+    return rowmajor ? kMatColumnTemps : kMatColumns;
+}
+
 static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX, int64_t ldx, int64_t nx,
                           char *dY, int64_t ldy, int64_t ny, double alpha, double beta, bool rowmajor,
                           hipStream_t s)
 {
     const int64_t esz = h->esz;
     int st = VBC_OK;
-    // the fused vector kernels read the merge layout and, from kMmSlotsMinRhs columns on, the slotted one
-    bool slotted = false;
-    bool fused = rowmajor && trans && nrhs > 0 && mulmat_fuses(h, &slotted);
-    if (slotted && nrhs < kMmSlotsMinRhs) fused = false;
-    if (trans ? (h->has_m && nrhs > 0 && h->n > 0) : (h->has_mf && nrhs > 0 && h->m > 0)) {  // matrix-core panels
+    const MatPath path = mat_path(h, trans, nrhs, rowmajor);
+    if (path == kMatPanels) {  // matrix-core panels
         const int64_t sxr = rowmajor ? ldx : 1, sxc = rowmajor ? 1 : ldx;
         const int64_t syr = rowmajor ? ldy : 1, syc = rowmajor ? 1 : ldy;
         return mulmat_panel_any(h, trans, nrhs, dX, sxr, sxc, dY, syr, syc, alpha, beta, s);
     }
-    if (fused) return mulmat_rowmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
-    if (!rowmajor) {
+    if (path == kMatFused) return mulmat_rowmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
+    if (path == kMatColumns) {
         for (int64_t r = 0; r < nrhs && st == VBC_OK; r++)
             st = mul_dispatch(h, trans, dX + r * ldx * esz, dY + r * ldy * esz, alpha, beta, s);
         return st;
@@ -3957,8 +3970,8 @@ static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX
     // row-major, per column through the handle's cached contiguous temporaries (strided 2D copies);
     // the caller holds h->mu, and the stream orders the columns -- no allocation, no synchronisation
     void *tx = nullptr, *ty = nullptr;
-    if (int e = stage_buffer(h, 2, std::max<int64_t>(nx, 1) * esz, &tx)) return e;
-    if (int e = stage_buffer(h, 3, std::max<int64_t>(ny, 1) * esz, &ty)) return e;
+    if (int e = stage_buffer(h, 2, std::max<int64_t>(nx, 1) * esz, s, &tx)) return e;
+    if (int e = stage_buffer(h, 3, std::max<int64_t>(ny, 1) * esz, s, &ty)) return e;
     for (int64_t r = 0; r < nrhs && st == VBC_OK; r++) {
         if (!copy2d(tx, esz, dX + r * esz, ldx * esz, esz, nx, hipMemcpyDeviceToDevice, s))
             st = fail(VBC_HIP_ERROR, "column gather failed");
@@ -3990,7 +4003,9 @@ int vbc_mul_mat(vbc_handle *h, int trans, int64_t nrhs, const void *X, int64_t l
     if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(h->mu);  // the fused kernel's carry buffer and the staging buffers
-    ProductOrder po(h, s, rowmajor);          // row-major per-column products share the column temporaries
+    // host operands share the X / Y staging buffers, row-major per-column products the column temporaries;
+    // panels hold no shared state
+    ProductOrder po(h, s, mem == VBC_MEM_HOST || mat_path(h, trans, nrhs, rowmajor) == kMatColumnTemps);
     if (mem == VBC_MEM_DEVICE) {
         int st = po.begin();
         if (st == VBC_OK)
@@ -4004,8 +4019,8 @@ int vbc_mul_mat(vbc_handle *h, int trans, int64_t nrhs, const void *X, int64_t l
     const int64_t xr = rowmajor ? nx : nrhs, xw = rowmajor ? nrhs : nx;  // rows x row-width (elements)
     const int64_t yr = rowmajor ? ny : nrhs, yw = rowmajor ? nrhs : ny;
     void *sx = nullptr, *sy = nullptr;
-    if (int st = stage_buffer(h, 0, xr * xw * esz, &sx)) return st;
-    if (int st = stage_buffer(h, 1, yr * yw * esz, &sy)) return st;
+    if (int st = stage_buffer(h, 0, xr * xw * esz, s, &sx)) return st;
+    if (int st = stage_buffer(h, 1, yr * yw * esz, s, &sy)) return st;
     if (int st = po.begin()) return st;
     if (!copy2d(sx, xw * esz, X, ldx * esz, xw * esz, xr, hipMemcpyHostToDevice, s))
         return fail(VBC_HIP_ERROR, "staging copy of X failed");
@@ -4223,10 +4238,10 @@ int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int64_t inc
     ProductOrder po(h, s, true);
     void *dx = const_cast<void *>(x), *dy = y;
     if (!direct_x) {
-        if (int st = stage_buffer(h, 0, nx * esz, &dx)) return st;
+        if (int st = stage_buffer(h, 0, nx * esz, s, &dx)) return st;
     }
     if (!direct_y) {
-        if (int st = stage_buffer(h, 1, ny * esz, &dy)) return st;
+        if (int st = stage_buffer(h, 1, ny * esz, s, &dy)) return st;
     }
     if (int st = po.begin()) return st;
     if (!direct_x) {
@@ -4282,7 +4297,7 @@ int vbc_update_values(vbc_handle *h, const void *val, int64_t nval, int val_dtyp
     std::lock_guard<std::mutex> lk(h->mu);
     const size_t bytes = (size_t)h->nval * elem_size(val_dtype);
     void *dv = nullptr;
-    if (int st = stage_buffer(h, 0, bytes, &dv)) return st;
+    if (int st = stage_buffer(h, 0, bytes, s, &dv)) return st;
     ProductOrder po(h, s, true);
     if (int st = po.begin()) return st;
     if (hipMemcpyAsync(dv, val, bytes, hipMemcpyHostToDevice, s) != hipSuccess)

@@ -187,6 +187,17 @@ bool mulmat_fuses(const vbc_handle *h, bool *slotted);
 constexpr int64_t kMmSlotsMinRhs = 2;  // smallest nrhs the slotted part runs fused at (profiles/mm_slots_time.json)
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
+// A cached buffer of the handle (`what`) has to grow for a product on `s`.  hipFree / hipMalloc are not stream
+// operations, so a product on a capturing stream is refused before either is called (the capture stays valid);
+// asked only when a buffer must grow, so a handle whose paths have each run once pays nothing.
+inline int may_grow(hipStream_t s, const char *what)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) return fail(VBC_HIP_ERROR, "hipStreamIsCapturing failed");
+    if (cs == hipStreamCaptureStatusNone) return VBC_OK;
+    set_error("%s must be allocated and the stream is capturing: run the product once outside the capture", what);
+    return VBC_INVALID_ARG;
+}
 void occupancy_ranges(int esz, int K, int P, int occ[2]);
 // vbc_generic.hip
 int mul_int(const vbc_handle *h, int trans, const void *x, void *y, double alpha, double beta, hipStream_t s);

@@ -308,19 +308,20 @@ static int mulmat_t_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t
                              double alpha, double beta, hipStream_t s)
 {
     const Launch &L = h->lt;
-    if (L.slot_ranges > 0)  // the slotted bins (their own stripes of y) first, as launch_group orders them
-        if (int st = mulmat_slots(h, nrhs, X, ldx, Y, ldy, alpha, beta, s)) return st;
     const int NRmax = 64;
     int64_t stride = 1;
     for (const Bin &b : L.bins) stride = std::max<int64_t>(stride, (int64_t)b.nranges * b.w * NRmax);
     const size_t need = (size_t)std::max<size_t>(L.bins.size(), 1) * stride * sizeof(T);
-    if (!L.bins.empty() && h->carry_mm_bytes < need) {  // (carry slots of the merge bins only)
+    if (!L.bins.empty() && h->carry_mm_bytes < need) {  // (carry slots of the merge bins only; before any launch)
+        if (int st = may_grow(s, "the multi-RHS carry buffer")) return st;
         if (h->d_carry_mm) (void)hipFree(h->d_carry_mm);
         h->d_carry_mm = nullptr;
         h->carry_mm_bytes = 0;
         VBC_HIP(hipMalloc(&h->d_carry_mm, need));
         h->carry_mm_bytes = need;
     }
+    if (L.slot_ranges > 0)  // the slotted bins (their own stripes of y) first, as launch_group orders them
+        if (int st = mulmat_slots(h, nrhs, X, ldx, Y, ldy, alpha, beta, s)) return st;
     T *cm = static_cast<T *>(h->d_carry_mm);
     const bool rd = beta != 0.0;
     for (int64_t c0 = 0; c0 < nrhs; c0 += NRmax) {

@@ -1,6 +1,7 @@
 """libvbc products captured into a HIP graph (torch.cuda.CUDAGraph = hipGraph on ROCm) replay to the
 same bits as eager launches: the VBC_MEM_DEVICE path launches on the caller's stream and never
-allocates, synchronises or copies once the handle exists (tools/graph_bench.py measures the gain)."""
+allocates, synchronises or copies once each path has run once (tools/graph_bench.py measures the gain;
+tests/test_gpu_graph_paths.py captures the paths that allocate on their first product)."""
 import numpy as np
 import pytest
 
