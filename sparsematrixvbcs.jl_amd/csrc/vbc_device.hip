@@ -1,7 +1,8 @@
-// libvbc handle creation and the C ABI of include/vbc.h.  A create is three steps: the device's facts
-// (gather_facts), the layout planned on the host alone (plan_layout: the builders below fill an arena image and
-// launch descriptors without device pointers from a LayoutConfig -- no HIP call, no environment), and the
-// device part (instantiate: upload, device pointers, fork streams and events).
+// libvbc's layout planner and the device part of the C ABI of include/vbc.h.  A create (vbc_create.hip: the entry
+// points and their host-side checks) is three steps: the device's facts (gather_facts), the layout planned on the
+// host alone (plan_layout, vbc_plan.h: the builders below fill an arena image and launch descriptors without device
+// pointers from a LayoutConfig -- no HIP call, no environment), and the device part (instantiate: upload, device
+// pointers, fork streams and events).  The products, vbc_get_info and vbc_update_values follow.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,36 +17,12 @@
 #include <vector>
 
 #include "vbc_handle.h"
+#include "vbc_plan.h"
 #include "vbc_planar.h"
 
 namespace vbc {
 
 static thread_local std::string g_err;
-
-// The recorder of VBC_CREATE_UPDATABLE's recording plans (create_handle below): the byte ranges of the arena
-// filled from transpose_stripes' values (the value map marks their slots, vbc_handle.h).  With a recorder
-// transpose_stripes copies the (tag) values instead of summing them.  `narrow`: the byte ranges of the value
-// regions stored as Float32 on a Float64 handle (VBC_CREATE_NARROW_UPDATABLE), in arena order; the builders that
-// narrow copy a tag's low 4 bytes there (narrow_value).  `ft_narrow`: whether the handle's own plan kept narrow
-// storage in the forward-on-Bᵀ layout (plan_layout's guard reads values, which a recording plan does not have).
-struct Recorder {
-    ByteRanges canon;
-    ByteRanges narrow;
-    bool ft_narrow = false;
-};
-
-// What the builders write besides the arena: which layouts exist and their statistics.
-struct PlanStats {
-    bool has_t = false, has_f = false, has_ft = false, has_m = false, has_mf = false;
-    bool f_scale = false;          // forward with several buckets: scale y by beta first
-    int64_t bytes_t = 0, bytes_f = 0, bytes_m = 0, bytes_mf = 0;  // matrix bytes one product streams
-    int32_t mf_group = 0;          // forward panel: widest output row group
-    int64_t panel_val_bytes = 0;   // largest bin val array of the panel layout
-    bool ft_narrow = false;        // the forward-on-Bᵀ layout kept narrow storage (plan_layout's guard)
-    // scratch of build_transposed, rebuilt by each call:
-    int small_split = 0;           // > 1: this B'x layout is the fused small-matrix split with P waves per chunk
-    uint32_t fuse_w = 0;           // bit w: the width-w bucket belongs to the fused split (all, or the side buckets)
-};
 
 // What the builders see (as `h`): the configuration, the statistics they fill, the recorder (NULL outside a
 // recording plan).  No handle, no device.
@@ -89,40 +66,6 @@ void set_error(const char *fmt, ...)
     va_end(ap);
     g_err = buf;
 }
-
-// Restores the caller's current device on scope exit.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-// Arena builder: reserves aligned regions, fills a host image, uploads once.
-struct Arena {
-    std::vector<char> host;
-    size_t reserve(size_t bytes)
-    {
-        size_t off = (host.size() + 255) & ~size_t(255);
-        host.resize(off + std::max<size_t>(bytes, 1));
-        return off;
-    }
-    template <typename U>
-    U *at(size_t off) { return reinterpret_cast<U *>(host.data() + off); }
-};
-
-struct PendingBin {
-    Bin b;
-    size_t o_key, o_val, o_rseg, o_out, o_carry, o_cseg;
-    double work = 0;  // matrix bytes the bin streams (launch-group ordering)
-};
 
 static int check_limits(const Stripes &s)
 {
@@ -214,18 +157,6 @@ static int build_bucket(PlanCtx *h, int kind, int w, const std::vector<Entry> &e
 }
 
 // ---- slotted layout (vbc_slots.h) ----------------------------------------------------------------
-
-struct PendingSlot {
-    SlotBin b;
-    size_t o_key, o_val, o_out, o_rrow, o_rchunk, o_base = 0, o_doff = 0, o_nlive = 0;
-    size_t o_trow = 0, o_tseg = 0, o_lseg = 0;  // lanes layout (build_lanes)
-    bool lanes_done = false;                    // keys already stored (build_lanes: 32-bit keys per run)
-    int64_t key_bytes = 0;       // index bytes as stored (keys, deltas, bases, delta offsets)
-    std::vector<uint32_t> keys;  // full keys until commit_slot_keys picks the stored form
-    int64_t rows = 0;
-    int64_t real = 0;            // entries without padding
-    bool kc_ok = false;          // every row's keys fit base + int16 deltas
-};
 
 // Per-row base of the compressed form: the first non-padding key of the row (0 if none).
 static bool slot_keys_compressible(const std::vector<uint32_t> &keys, int64_t rows, int RPI)
@@ -1040,12 +971,6 @@ static void commit_launch_keys(const PlanCtx *h, std::vector<PendingSlot> &pss, 
 
 // ---- row-swept layout (vbc_sweep.hip) ------------------------------------------------------------
 
-struct PendingSweep {
-    SweepBin b;
-    size_t o_tstep, o_key, o_loc, o_val, o_out, o_sbase;
-    double work = 0;  // matrix bytes the bin streams (launch-group ordering)
-};
-
 // Whether a bucket lacks x locality: the gathers of windows of 64 consecutive segments (the segments
 // one slotted chunk folds together) span most of an x (length nx) too large for L2.  Mesh operators
 // span a few bandwidths (FE: ~10^4 rows of 10^7); the costs.jl:63-83 generator spans all of x.
@@ -1384,9 +1309,8 @@ static bool column_pieces(const PlanCtx *h, const Stripes &s, Stripes &c)
 // Transposed layout: segments = stripes of each width, entries = their stored rows.  A bucket runs
 // slotted (vbc_slots.h, every stripe of the width a segment, empty ones included) when its row counts
 // are near-uniform, else merged (non-empty stripes; empty ones go to the fill list).
-static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Arena &ar,
-                            std::vector<PendingBin> &pbs, std::vector<PendingSlot> &pss,
-                            std::vector<PendingSweep> &pws, Launch &L, std::vector<int32_t> &fill)
+static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Arena &ar, LaunchPlan &plan,
+                            std::vector<int32_t> &fill)
 {
     Stripes sp;
     const Stripes &s = column_pieces(h, s0, sp) ? sp : s0;
@@ -1563,7 +1487,7 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
                 PendingSweep pw;
                 if (int st = build_sweep(h, 0, w, sb, ents, out, val, ar, tile0, pw)) return st;
                 pw.work = (double)ents.size() * (4.0 + (double)w * h->esz);
-                pws.push_back(pw);
+                plan.sweeps.push_back(pw);
                 continue;
             }
         }
@@ -1609,7 +1533,7 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
             }
             PendingSlot ps;
             if (int st = build_ksplit(h, w, ks, ents, sbeg, out, total, val, ar, srange0, ps)) return st;
-            pss.push_back(std::move(ps));
+            plan.slots.push_back(std::move(ps));
             continue;
         }
         if (want_slots(h, 0, wps, sb, hsbeg.empty() ? total : total + (hsbeg.back() - sbeg.back()), s.m, order, &mask, w)) {
@@ -1632,7 +1556,7 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
             } else if (int st = build_slots(h, 0, wps, w, ents, sbeg, out, total, val, ar, srange0, ps, order, mask)) {
                 return st;
             }
-            pss.push_back(std::move(ps));
+            plan.slots.push_back(std::move(ps));
             continue;
         }
         std::vector<Entry> ents;
@@ -1652,10 +1576,10 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
         if (int st = build_bucket(h, 0, wp, ents, out, total, val, ar, range0, pb, w)) return st;
         h->st.bytes_t += (int64_t)ents.size() * (4 + (int64_t)wp * h->esz) + (int64_t)out.size() * 4;
         pb.work = (double)ents.size() * (4.0 + (double)wp * h->esz);
-        pbs.push_back(pb);
+        plan.bins.push_back(pb);
     }
-    commit_launch_keys(h, pss, ar);
-    for (const PendingSlot &ps : pss) {  // slotted bins: padded rows x (index bytes + values)
+    commit_launch_keys(h, plan.slots, ar);
+    for (const PendingSlot &ps : plan.slots) {  // slotted bins: padded rows x (index bytes + values)
         if (ps.b.lanes) {  // lanes: real rows' values, one key per run, nlive per row, the tile tables
             h->st.bytes_t += ps.real * (int64_t)ps.b.w * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes + ps.rows * 4 + (int64_t)ps.b.ntiles * (8 + 128);
         } else if (ps.b.mask) {  // masked: padding lanes fetch nothing; + the per-row live counts
@@ -1665,12 +1589,12 @@ static int build_transposed(PlanCtx *h, const Stripes &s0, const char *val, Aren
             h->st.bytes_t += ps.rows * ps.b.rpi * (int64_t)ps.b.w * (ps.b.pair ? 3 : 1) * (ps.b.vsz ? ps.b.vsz : h->esz) + ps.key_bytes;
         }
     }
-    L.total_ranges = range0;
-    L.slot_ranges = srange0;
-    L.sweep_tiles = tile0;
-    L.fuse_p = h->st.small_split;  // (the handle's field is rebuilt by the next build_transposed call)
-    L.sweep_tile_bytes = h->sweep_tile;
-    L.sweep_diag = h->sweep_diag;
+    plan.L.total_ranges = range0;
+    plan.L.slot_ranges = srange0;
+    plan.L.sweep_tiles = tile0;
+    plan.L.fuse_p = h->st.small_split;  // (the handle's field is rebuilt by the next build_transposed call)
+    plan.L.sweep_tile_bytes = h->sweep_tile;
+    plan.L.sweep_diag = h->sweep_diag;
     h->st.bytes_t += (s.m + s.n) * h->esz;  // x read once, y written once
     return VBC_OK;
 }
@@ -1976,9 +1900,8 @@ static bool fwd_via_t_wanted(const PlanCtx *h, const Stripes &s, unsigned flags)
     return mixed || h->fwd_t == 2;
 }
 
-static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
-                         std::vector<std::vector<PendingBin>> &pbs, std::vector<std::vector<PendingSlot>> &pss,
-                         std::vector<std::vector<PendingSweep>> &pws, std::vector<Launch> &Ls,
+// One LaunchPlan per width bucket.
+static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &ar, std::vector<LaunchPlan> &plans,
                          std::vector<int32_t> &fill)
 {
     std::map<int, std::vector<int64_t>> buckets;  // w -> stripes
@@ -2011,13 +1934,11 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                 if (int st = build_sweep(h, 1, w, sb, ents, out, val, ar, tile0, pw)) return st;
                 h->st.bytes_f += s.m * h->esz;  // y written once per bucket
                 std::fill(any.begin(), any.end(), 1);
-                Ls.emplace_back();
-                Ls.back().sweep_tiles = tile0;
-                Ls.back().sweep_tile_bytes = h->sweep_tile;
-                Ls.back().sweep_diag = h->sweep_diag;
-                pbs.push_back({});
-                pss.push_back({});
-                pws.push_back({pw});
+                plans.emplace_back();
+                plans.back().L.sweep_tiles = tile0;
+                plans.back().L.sweep_tile_bytes = h->sweep_tile;
+                plans.back().L.sweep_diag = h->sweep_diag;
+                plans.back().sweeps.push_back(pw);
                 continue;
             }
         }
@@ -2035,7 +1956,7 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                 const int64_t e = cur[i]++;
                 ents[e] = {(uint32_t)s.col0[l] | (!slotted && e == cnt[i] ? kHead : 0u), s.voff[l] + (r - s.rbeg[l]) * w};
             }
-        Ls.emplace_back();
+        plans.emplace_back();
         if (single) {  // node-blocked rows: the planar forward layout with row runs (or lane streams)
             const int R = fwd_runs(h, w, s.m, ents, sbeg);
             PendingSlot ps;
@@ -2065,9 +1986,7 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
                     h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * R * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
                                      s.m * h->esz;
                 std::fill(any.begin(), any.end(), 1);
-                pbs.push_back({});
-                pss.push_back(std::move(one));
-                pws.push_back({});
+                plans.back().slots = std::move(one);
                 continue;
             }
         }
@@ -2082,10 +2001,8 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
             h->st.bytes_f += p1.rows * p1.b.rpi * (int64_t)w * (p1.b.vsz ? p1.b.vsz : h->esz) + p1.key_bytes +
                           (int64_t)sout.size() * h->esz;
             for (int32_t i : sout) any[i] = 1;
-            pbs.push_back({});
-            pss.push_back(std::move(one));
-            pws.push_back({});
-            Ls.back().slot_ranges = srange0;
+            plans.back().slots = std::move(one);
+            plans.back().L.slot_ranges = srange0;
             continue;
         }
         std::vector<int32_t> out;
@@ -2095,10 +2012,8 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
         int range0 = 0;
         if (int st = build_bucket(h, 1, w, ents, out, (int64_t)ents.size(), val, ar, range0, pb)) return st;
         h->st.bytes_f += (int64_t)ents.size() * (4 + (int64_t)w * h->esz) + (int64_t)out.size() * (4 + h->esz);
-        pbs.push_back({pb});
-        pss.push_back({});
-        pws.push_back({});
-        Ls.back().total_ranges = range0;
+        plans.back().bins.push_back(pb);
+        plans.back().L.total_ranges = range0;
     }
     h->st.f_scale = buckets.size() > 1;
     if (buckets.size() <= 1)
@@ -2108,13 +2023,6 @@ static int build_forward(PlanCtx *h, const Stripes &s, const char *val, Arena &a
     h->st.bytes_f += s.n * h->esz;
     return VBC_OK;
 }
-
-struct PendingPanel {
-    PanelBin b;
-    TileBin tb;  // tile: a small-tile bucket (vbc_tiles.h; o_rgrp = its range table)
-    bool tile = false;
-    size_t o_key, o_val, o_out, o_rgrp, o_rseg;
-};
 
 // Tile layout (vbc_tiles.h) of one width bucket (w <= 4, whole stripes) of the multi-RHS product: each
 // stripe's stored rows grouped into tiles of consecutive rows of one row group -- Π's block rows (tgrp:
@@ -2447,9 +2355,8 @@ static bool build_tiles(PlanCtx *h, const Stripes &s, const std::vector<int64_t>
 // Panel layout (vbc_panel.h) of the transposed product: per width bucket (stripes wider than 16 are
 // cut into 16-column pieces that share the stripe's rows), S = 16/w consecutive stripes per panel,
 // each panel's rows padded to a multiple of 4, ranges of whole panels balanced by rows.
-static int build_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
-                       std::vector<PendingPanel> &pps, PanelLaunch &L, std::vector<int32_t> &fill,
-                       const std::vector<int64_t> *tgrp)
+static int build_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar, PanelPlan &plan,
+                       std::vector<int32_t> &fill, const std::vector<int64_t> *tgrp)
 {
     struct Piece {
         int64_t l;
@@ -2472,7 +2379,7 @@ static int build_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
         }
         PendingPanel pp;
         if (whole && build_tiles(h, s, st, it->first, tgrp, val, ar, pp)) {
-            pps.push_back(pp);
+            plan.bins.push_back(pp);
             it = buckets.erase(it);
         } else {
             ++it;
@@ -2568,9 +2475,9 @@ static int build_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
             std::memset(vv + row * w * esz, 0, (size_t)w * esz);
         }
         h->st.bytes_m += Rp * (4 + (int64_t)w * esz) + (int64_t)out.size() * 4;
-        pps.push_back(pp);
+        plan.bins.push_back(pp);
     }
-    L.total_ranges = range0;
+    plan.L.total_ranges = range0;
     return VBC_OK;
 }
 
@@ -2692,8 +2599,7 @@ static int transpose_stripes(const PlanCtx *h, const Stripes &s, const char *val
 
 // Forward panel layout (VBC_CREATE_MULTI_FORWARD): Y = B·X is the transposed product of C = Bᵀ, so the
 // transposed panel layout of C (transpose_stripes, groups up to 16 rows) serves it.
-static int build_forward_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar,
-                               std::vector<PendingPanel> &pps, PanelLaunch &L)
+static int build_forward_panel(PlanCtx *h, const Stripes &s, const char *val, Arena &ar, PanelPlan &plan)
 {
     Stripes c;
     std::vector<char> cv;
@@ -2708,7 +2614,7 @@ static int build_forward_panel(PlanCtx *h, const Stripes &s, const char *val, Ar
     std::vector<int64_t> cg;
     for (int64_t l = 0; l < s.L; l++) cg.push_back(s.col0[l]);
     cg.push_back(s.n);
-    const int st = build_panel(h, c, cv.data(), ar, pps, L, fill, &cg);
+    const int st = build_panel(h, c, cv.data(), ar, plan, fill, &cg);
     h->st.bytes_mf = h->st.bytes_m - bytes0;
     h->st.bytes_m = bytes0;
     return st;
@@ -2725,12 +2631,13 @@ static int upload_bins(const std::vector<B> &bins, B *&d_bins)
     return VBC_OK;
 }
 
-static int finalize_panel(vbc_handle *h, const std::vector<PendingPanel> &pps, PanelLaunch &L)
+// The device pointers of a planned panel launch, into L: the handle's descriptor, moved there from the plan.
+static int finalize_panel(vbc_handle *h, const PanelPlan &plan, PanelLaunch &L)
 {
     L.bins.clear();
     L.tbins.clear();
     char *base = static_cast<char *>(h->d_arena);
-    for (const PendingPanel &pp : pps) {
+    for (const PendingPanel &pp : plan.bins) {
         if (pp.tile) {
             TileBin t = pp.tb;
             t.key = reinterpret_cast<const uint32_t *>(base + pp.o_key);
@@ -2752,14 +2659,14 @@ static int finalize_panel(vbc_handle *h, const std::vector<PendingPanel> &pps, P
     return upload_bins(L.bins, L.d_bins);
 }
 
-static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, const std::vector<PendingSlot> &pss,
-                           Launch &L, const std::vector<PendingSweep> &pws)
+// The same for a planned launch (an empty plan: a forward product with no entries, its fill list alone writes y).
+static int finalize_launch(vbc_handle *h, const LaunchPlan &plan, Launch &L)
 {
     L.bins.clear();
     L.sbins.clear();
     L.wbins.clear();
     char *base = static_cast<char *>(h->d_arena);
-    for (const PendingSweep &pw : pws) {
+    for (const PendingSweep &pw : plan.sweeps) {
         SweepBin b = pw.b;
         b.tstep = reinterpret_cast<const int32_t *>(base + pw.o_tstep);
         b.key = reinterpret_cast<const uint32_t *>(base + pw.o_key);
@@ -2770,7 +2677,7 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         L.wbins.push_back(b);
     }
     if (int st = upload_bins(L.wbins, L.d_wbins)) return st;
-    for (const PendingBin &pb : pbs) {
+    for (const PendingBin &pb : plan.bins) {
         Bin b = pb.b;
         b.key = reinterpret_cast<const uint32_t *>(base + pb.o_key);
         b.val = base + pb.o_val;
@@ -2781,7 +2688,7 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         L.bins.push_back(b);
     }
     L.pbins.clear();
-    for (const PendingSlot &ps : pss) {
+    for (const PendingSlot &ps : plan.slots) {
         SlotBin b = ps.b;
         b.key = reinterpret_cast<const uint32_t *>(base + ps.o_key);
         b.val = base + ps.o_val;
@@ -2836,14 +2743,14 @@ static int finalize_launch(vbc_handle *h, const std::vector<PendingBin> &pbs, co
         std::vector<double> pw_planar;
         double slots = 0, fused = 0, sweep = 0, merge = 0;
         size_t pi = 0;
-        for (const PendingSlot &ps : pss) {
+        for (const PendingSlot &ps : plan.slots) {
             const double wk = (double)ps.rows * ps.b.rpi * ps.b.w * h->esz + (double)ps.key_bytes;
             if (!ps.b.planar) slots += wk;
             else if (L.fuse_split && L.pbins[pi++].fused) fused += wk;
             else pw_planar.push_back(wk);
         }
-        for (const PendingSweep &pw : pws) sweep += pw.work;
-        for (const PendingBin &pb : pbs) merge += pb.work;
+        for (const PendingSweep &pw : plan.sweeps) sweep += pw.work;
+        for (const PendingBin &pb : plan.bins) merge += pb.work;
         if (L.sweep_tiles > 0) L.gwork.push_back(sweep);
         if (L.slot_ranges > 0) L.gwork.push_back(slots);
         if (L.fuse_split) L.gwork.push_back(fused);
@@ -2897,7 +2804,7 @@ void PanelLaunch::free_device()
     if (d_bins) (void)hipFree(d_bins);
 }
 
-static void release(vbc_handle *h)
+void release(vbc_handle *h)
 {
     if (!h) return;
     DeviceGuard g(h->device);
@@ -2915,42 +2822,7 @@ static void release(vbc_handle *h)
     delete h;
 }
 
-template <typename T>
-static int64_t count_nonzeros(const char *val, int64_t n)
-{
-    const T *v = reinterpret_cast<const T *>(val);
-    int64_t c = 0;
-    for (int64_t i = 0; i < n; i++) c += (v[i] != T(0));
-    return c;
-}
-
-// Integer eltypes: arena offsets of IntLayout.
-struct IntPlan {
-    int64_t L = 0, nrows = 0;
-    size_t o_col0 = 0, o_w = 0, o_rows = 0, o_c2s = 0, o_r2s = 0, o_rbeg = 0, o_voff = 0, o_val = 0;
-};
-
-// What plan_layout makes and instantiate uploads: the arena image, per direction the pending bins (arena
-// offsets) and the host descriptors without device pointers -- transposed (t), forward as the transposed product
-// of C = Bᵀ (tf), forward with one launch per width bucket (f), panels (m, mf) -- and the statistics.
-struct Plan {
-    Arena ar;
-    bool is_int = false;
-    IntPlan li;
-    std::vector<PendingBin> pt, ptf;
-    std::vector<PendingSlot> st_t, stf;
-    std::vector<PendingSweep> sw_t, swf;
-    std::vector<std::vector<PendingBin>> pf;
-    std::vector<std::vector<PendingSlot>> sf;
-    std::vector<std::vector<PendingSweep>> wf;
-    std::vector<PendingPanel> pm, pmf;
-    Launch lt, lft;
-    std::vector<Launch> lf;
-    PanelLaunch lm, lmf;
-    PlanStats st;
-};
-
-static int check_plan_input(int dtype, const Stripes &s)
+int check_plan_input(int dtype, const Stripes &s)
 {
     if (dtype != VBC_F64 && dtype != VBC_F32 && dtype != VBC_I64)
         return fail(VBC_UNSUPPORTED_DTYPE, "GPU products compute in Float64, Float32 or Int64 (see vbc_types)");
@@ -2991,9 +2863,7 @@ static void place_fill(Arena &ar, LaunchT &L, const std::vector<int32_t> &fill)
     if (!fill.empty()) std::memcpy(ar.at<int32_t>(L.o_fill), fill.data(), fill.size() * 4);
 }
 
-// Plans every layout `flags` asks for (none of the four layout flags: the transposed one).  v: nval elements
-// of cfg.dtype.  Pure host code: no HIP call, no environment.
-static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v, int64_t nval, unsigned flags, Plan &P,
+int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v, int64_t nval, unsigned flags, Plan &P,
                 Recorder *rec)
 {
     if (int st = check_plan_input(cfg.dtype, s)) return st;
@@ -3013,22 +2883,22 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
     std::vector<int32_t> fill;
     int st = VBC_OK;
     if (flags & VBC_CREATE_MULTI) {
-        st = build_panel(h, s, v, ar, P.pm, P.lm, fill, nullptr);
+        st = build_panel(h, s, v, ar, P.m, fill, nullptr);
         h->st.has_m = st == VBC_OK;
-        if (st == VBC_OK) place_fill(ar, P.lm, fill);
+        if (st == VBC_OK) place_fill(ar, P.m.L, fill);
     }
     if (st == VBC_OK && (flags & VBC_CREATE_MULTI_FORWARD)) {
         const size_t c0 = ar.host.size();
-        st = build_forward_panel(h, s, v, ar, P.pmf, P.lmf);
+        st = build_forward_panel(h, s, v, ar, P.mf);
         if (rec) rec->canon.emplace_back(c0, ar.host.size());
         h->st.has_mf = st == VBC_OK;
-        if (st == VBC_OK) P.lmf.o_fill = ar.reserve(4);
+        if (st == VBC_OK) P.mf.L.o_fill = ar.reserve(4);
     }
     if (st == VBC_OK && (flags & VBC_CREATE_TRANSPOSED)) {
         fill.clear();
-        st = build_transposed(h, s, v, ar, P.pt, P.st_t, P.sw_t, P.lt, fill);
+        st = build_transposed(h, s, v, ar, P.t, fill);
         h->st.has_t = st == VBC_OK;
-        if (st == VBC_OK) place_fill(ar, P.lt, fill);
+        if (st == VBC_OK) place_fill(ar, P.t.L, fill);
     }
     fill.clear();
     if (st == VBC_OK && (flags & VBC_CREATE_FORWARD) && fwd_via_t_wanted(h, s, flags)) {
@@ -3053,21 +2923,21 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
             cfg_c.narrow_swept = cfg.narrow_swept && cfg_c.narrow_values;
             h->st.ft_narrow = cfg_c.narrow_values;
             PlanCtx hc(cfg_c, P.st, rec, nval);
-            st = build_transposed(&hc, c, cv.data(), ar, P.ptf, P.stf, P.swf, P.lft, fill);
+            st = build_transposed(&hc, c, cv.data(), ar, P.tf, fill);
             if (rec) rec->canon.emplace_back(c0, ar.host.size());
             h->st.bytes_f = h->st.bytes_t - bt;
             h->st.bytes_t = bt;
         }
         if (st == VBC_OK) {
             h->st.has_f = h->st.has_ft = true;
-            place_fill(ar, P.lft, fill);
+            place_fill(ar, P.tf.L, fill);
         }
     } else if (st == VBC_OK && (flags & VBC_CREATE_FORWARD)) {
-        st = build_forward(h, s, v, ar, P.pf, P.sf, P.wf, P.lf, fill);
+        st = build_forward(h, s, v, ar, P.f, fill);
         h->st.has_f = st == VBC_OK;
         if (st == VBC_OK) {
-            if (P.lf.empty()) P.lf.emplace_back();  // no entries: the fill list alone writes y
-            place_fill(ar, P.lf[0], fill);
+            if (P.f.empty()) P.f.emplace_back();  // no entries: the fill list alone writes y
+            place_fill(ar, P.f[0].L, fill);
         }
     }
     return st;
@@ -3075,7 +2945,7 @@ static int plan_layout(const LayoutConfig &cfg, const Stripes &s, const char *v,
 
 // What a create asks the device (the current one, ordinal `device`): the rows of the eltypes in `eltypes`
 // (bit 0: Float64, bit 1: Float32), the panel / tile rows only with `multi`.
-static int gather_facts(int device, unsigned eltypes, bool multi, DeviceFacts &f)
+int gather_facts(int device, unsigned eltypes, bool multi, DeviceFacts &f)
 {
     f = DeviceFacts{};
     hipDeviceProp_t prop;
@@ -3124,28 +2994,28 @@ static int instantiate_on_device(vbc_handle *h, Plan &P)
         li.val = reinterpret_cast<const int64_t *>(b + P.li.o_val);
         return VBC_OK;
     }
-    h->lt = std::move(P.lt);
-    h->lft = std::move(P.lft);
-    h->lf = std::move(P.lf);
-    h->lm = std::move(P.lm);
-    h->lmf = std::move(P.lmf);
+    h->lt = std::move(P.t.L);
+    h->lft = std::move(P.tf.L);
+    for (LaunchPlan &lp : P.f) h->lf.push_back(std::move(lp.L));
+    h->lm = std::move(P.m.L);
+    h->lmf = std::move(P.mf.L);
     int st = VBC_OK;
-    if (h->has_t && (st = finalize_launch(h, P.pt, P.st_t, h->lt, P.sw_t))) return st;
-    if (h->has_ft && (st = finalize_launch(h, P.ptf, P.stf, h->lft, P.swf))) return st;
+    if (h->has_t && (st = finalize_launch(h, P.t, h->lt))) return st;
+    if (h->has_ft && (st = finalize_launch(h, P.tf, h->lft))) return st;
     if (h->has_t && (st = fork_streams(h, h->lt))) return st;
     if (h->has_ft && (st = fork_streams(h, h->lft))) return st;
-    if (h->has_m && (st = finalize_panel(h, P.pm, h->lm))) return st;
-    if (h->has_mf && (st = finalize_panel(h, P.pmf, h->lmf))) return st;
-    for (size_t b = 0; b < P.pf.size(); b++)
-        if ((st = finalize_launch(h, P.pf[b], P.sf[b], h->lf[b], P.wf[b]))) return st;
-    if (h->has_f && !h->has_ft && P.pf.empty() && (st = finalize_launch(h, {}, {}, h->lf[0], {}))) return st;
+    if (h->has_m && (st = finalize_panel(h, P.m, h->lm))) return st;
+    if (h->has_mf && (st = finalize_panel(h, P.mf, h->lmf))) return st;
+    // (a forward layout with no entries is one empty LaunchPlan: the fill list alone writes y)
+    for (size_t b = 0; b < P.f.size(); b++)
+        if ((st = finalize_launch(h, P.f[b], h->lf[b]))) return st;
     h->has_scratch = (h->has_t && !h->lt.bins.empty()) || (h->has_ft && !h->lft.bins.empty());
     for (const Launch &l : h->lf) h->has_scratch = h->has_scratch || (h->has_f && !l.bins.empty());
     return VBC_OK;
 }
 
 // Uploads a plan's arena to `device` and builds the handle around it (the caller fills the matrix dimensions).
-static int instantiate(Plan &P, const LayoutConfig &cfg, int device, vbc_handle **out)
+int instantiate(Plan &P, const LayoutConfig &cfg, int device, vbc_handle **out)
 {
     vbc_handle *h = new vbc_handle(cfg);
     h->dtype = cfg.dtype;
@@ -3172,120 +3042,6 @@ static int instantiate(Plan &P, const LayoutConfig &cfg, int device, vbc_handle 
 
 using namespace vbc;
 
-// The reference's fields as Stripes, with the checks of its inner constructors: shared by the creates and
-// vbcx_plan_image.  nval: the elements of val the stripes address.
-struct StripesInput {
-    Stripes s;
-    int64_t nval = 0, K = 0, nblocks = 0;
-};
-
-// A create after its entry's own checks.  build(v, in, val): the entry's stripes and the values they address,
-// from the caller's values (v = NULL) or from an array of the same shape (the recording plans below).
-// Order: the checks, the device's facts, the plan with the caller's values, the device part; then, for
-// VBC_CREATE_UPDATABLE, two recording plans of the same pattern on the host alone -- val all zero, val holding
-// the tag i + 1 in element i, written before any blocking or transposition of the values -- whose arenas differ
-// exactly in the value slots (vbc_update.hip build_value_map).
-
-// The two recording plans of an updatable create and the value map they give (vbc_update.hip value_map_host): pure
-// host code.  `ft_narrow`, `arena_used`: the forward-on-Bᵀ guard's answer and the image size of the plan made with
-// the caller's values, which the recording plans must reproduce.
-template <typename F>
-static int plan_value_map(const LayoutConfig &cfg, unsigned flags, StripesInput &in, F &&build, bool ft_narrow,
-                          size_t arena_used, std::vector<uint32_t> &map, std::vector<UpdChunk> &chunks)
-{
-    const int64_t nval = in.nval;
-    const size_t esz = (size_t)cfg.esz;
-    if (nval > kUpdMaxSource)
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE: val has more than 2^31 - 2 elements (the value map stores 32-bit source indices)");
-    int st = VBC_OK;
-    std::vector<char> arena[2];
-    Recorder rec;
-    std::vector<char> tv((size_t)std::max<int64_t>(nval, 1) * esz, 0);
-    for (int pass = 0; pass < 2 && st == VBC_OK; pass++) {
-        if (pass == 1)
-            for (int64_t i = 0; i < nval; i++) {
-                const uint64_t tag = (uint64_t)i + 1;
-                std::memcpy(tv.data() + (size_t)i * esz, &tag, esz);  // little-endian: the low esz bytes
-            }
-        rec = Recorder{};
-        rec.ft_narrow = ft_narrow;
-        Plan P;
-        const void *val = nullptr;
-        if ((st = build(tv.data(), in, val)) == VBC_OK)
-            st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, &rec);
-        arena[pass] = std::move(P.ar.host);
-    }
-    if (st != VBC_OK) return st;
-    tv = std::vector<char>();
-    if (arena[0].size() != arena_used)
-        return fail(VBC_INVALID_ARG, "internal: a recording build of an updatable handle chose another layout");
-    return value_map_host((int)esz, nval, arena[1], arena[0], rec.canon, rec.narrow, map, chunks);
-}
-
-template <typename F>
-static int create_handle(vbc_handle **out, int dtype, int device, unsigned flags, unsigned narrow, F &&build)
-{
-    // VBC_CREATE_NARROW_UPDATABLE arrives in `narrow` (check_narrow): the same map, with narrow chunks
-    const bool narrow_updatable = (narrow & VBC_CREATE_NARROW_UPDATABLE) != 0;
-    const bool updatable = (flags & VBC_CREATE_UPDATABLE) != 0 || narrow_updatable;
-    flags &= ~VBC_CREATE_UPDATABLE;
-    if (updatable && !out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
-    if (updatable) *out = nullptr;
-    StripesInput in;
-    const void *val = nullptr;
-    if (int st = build(nullptr, in, val)) return st;
-    if (!out) return fail(VBC_INVALID_ARG, "out handle pointer is NULL");
-    *out = nullptr;
-    if (int st = check_plan_input(dtype, in.s)) return st;
-    int ndev = 0;
-    VBC_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VBC_INVALID_ARG, "device ordinal out of range");
-    const char *v = static_cast<const char *>(val);
-    const int64_t nval = in.nval;
-    DeviceFacts facts{};
-    if (dtype != VBC_I64) {
-        DeviceGuard g(device);
-        if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
-        if (int st = gather_facts(device, dtype == VBC_F64 ? 1u : 2u,
-                                  (flags & (VBC_CREATE_MULTI | VBC_CREATE_MULTI_FORWARD)) != 0, facts))
-            return st;
-    }
-    const LayoutConfig cfg = make_config(dtype, flags, narrow, facts);
-    vbc_handle *h = nullptr;
-    bool ft_narrow = false;
-    {
-        Plan P;
-        if (int st = plan_layout(cfg, in.s, v, nval, flags, P, nullptr)) return st;
-        ft_narrow = P.st.ft_narrow;
-        if (int st = instantiate(P, cfg, device, &h)) return st;
-    }
-    h->m = in.s.m;
-    h->n = in.s.n;
-    h->L = in.s.L;
-    h->K = in.K;
-    h->nblocks = in.nblocks;
-    h->nrows = (int64_t)in.s.rows.size();
-    h->nval = nval;
-    h->nnz = dtype == VBC_F64 ? count_nonzeros<double>(v, nval)
-           : dtype == VBC_F32 ? count_nonzeros<float>(v, nval) : count_nonzeros<int64_t>(v, nval);
-    if (!updatable) {
-        *out = h;
-        return VBC_OK;
-    }
-    std::vector<uint32_t> map;
-    std::vector<UpdChunk> chunks;
-    int st = plan_value_map(cfg, flags, in, build, ft_narrow, h->arena_used, map, chunks);
-    if (st == VBC_OK) {
-        DeviceGuard g(h->device);
-        st = g.ok ? upload_value_map(h, map, chunks) : fail(VBC_HIP_ERROR, "hipSetDevice failed");
-    }
-    if (st != VBC_OK) { release(h); return st; }
-    h->umap.mixed = narrow_updatable;
-    h->updatable = true;
-    *out = h;
-    return VBC_OK;
-}
-
 extern "C" {
 
 static_assert(sizeof(vbc_info) == VBC_INFO_SIZE, "vbc_info layout changed: bump VBC_VERSION and VBC_INFO_SIZE");
@@ -3299,404 +3055,6 @@ int vbc_last_error(char *buf, size_t n)
         buf[n - 1] = 0;
     }
     return (int)g_err.size();
-}
-
-
-int vbcx_device_facts(int device, vbcx_facts *out)
-{
-    if (!out) return fail(VBC_INVALID_ARG, "NULL facts");
-    int ndev = 0;
-    VBC_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VBC_INVALID_ARG, "device ordinal out of range");
-    DeviceGuard g(device);
-    if (!g.ok) return fail(VBC_HIP_ERROR, "hipSetDevice failed");
-    return gather_facts(device, 3u, true, *out);
-}
-
-// VBC_CREATE_UPDATABLE_SHARDS belongs to the sharded creates (vbc_sharded.cpp), which pass VBC_CREATE_UPDATABLE on
-// to their shards; the plain and *_ex creates end here.
-static int refuse_narrow_flag(vbc_handle **out, const char *why)
-{
-    if (out) *out = nullptr;
-    return fail(VBC_INVALID_ARG, why);
-}
-constexpr unsigned kNarrowBits = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS |
-                                 VBC_CREATE_NARROW_STREAMS | VBC_CREATE_NARROW_SWEPT;
-constexpr const char *kNarrowSweptAlone = "VBC_CREATE_NARROW_SWEPT is valid only together with VBC_CREATE_NARROW_VALUES";
-constexpr const char *kNarrowSweptPlain = "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs Float32 values on a "
-                                          "Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
-                                          "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
-constexpr unsigned kNarrowBelowStreams = VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR | VBC_CREATE_NARROW_PAIRS;
-constexpr const char *kNarrowStreamsAlone = "VBC_CREATE_NARROW_STREAMS is valid only together with VBC_CREATE_NARROW_VALUES, "
-                                            "VBC_CREATE_NARROW_PLANAR and VBC_CREATE_NARROW_PAIRS";
-constexpr const char *kNarrowStreamsPlain = "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES, VBC_CREATE_NARROW_PLANAR "
-                                            "and VBC_CREATE_NARROW_PAIRS) needs Float32 values on a Float64 handle: pass it "
-                                            "to vbc1d_create_ex / vbc2d_create_ex / vbc_csc_create_ex (the creates without "
-                                            "vbc_types store the compute eltype)";
-constexpr const char *kNarrowPairsAlone = "VBC_CREATE_NARROW_PAIRS is valid only together with VBC_CREATE_NARROW_VALUES and "
-                                          "VBC_CREATE_NARROW_PLANAR";
-constexpr const char *kNarrowPlain = "VBC_CREATE_NARROW_VALUES (and VBC_CREATE_NARROW_PLANAR / VBC_CREATE_NARROW_PAIRS with it) needs Float32 values "
-                                     "on a Float64 handle: pass it to vbc1d_create_ex / vbc2d_create_ex / "
-                                     "vbc_csc_create_ex (the creates without vbc_types store the compute eltype)";
-constexpr const char *kNarrowUpdPlain = "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES, "
-                                        "which needs Float32 values on a Float64 handle: pass both to vbc1d_create_ex / "
-                                        "vbc2d_create_ex / vbc_csc_create_ex";
-
-static int refuse_sharded_flag(vbc_handle **out)
-{
-    if (out) *out = nullptr;
-    return fail(VBC_INVALID_ARG, "VBC_CREATE_UPDATABLE_SHARDS is a flag of the sharded creates (single handle: VBC_CREATE_UPDATABLE)");
-}
-
-
-static int stripes_1d(int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl, const int64_t *pos,
-               const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, StripesInput &in)
-{
-    // SparseMatrix1DVBC{W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:45-50)
-    if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
-    if (n < 0) return fail(VBC_INVALID_ARG, "number of columns (n) must be >= 0");
-    if (W <= 0) return fail(VBC_INVALID_ARG, "W must be > 0");
-    if (L < 0 || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad stripe arrays");
-    if (spl[0] != 1 || spl[L] != n + 1) return fail(VBC_INVALID_ARG, "Φ.spl must run from 1 to n+1");
-    if (pos[0] != 1 || ofs[0] != 1) return fail(VBC_INVALID_ARG, "pos[1] and ofs[1] must be 1");
-    Stripes &s = in.s;
-    s = Stripes{};
-    s.m = m; s.n = n; s.L = L;
-    s.col0.resize(L); s.w.resize(L); s.rbeg.resize(L + 1); s.voff.resize(L);
-    const int64_t q = pos[L] - 1;
-    if (q < 0 || (q > 0 && !idx)) return fail(VBC_INVALID_ARG, "bad pos");
-    if (ofs[L] - 1 > nval) return fail(VBC_INVALID_ARG, "val shorter than ofs[L+1]-1");
-    if (ofs[L] - 1 > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
-    for (int64_t l = 0; l < L; l++) {
-        const int64_t w = spl[l + 1] - spl[l];
-        if (w < 1) return fail(VBC_INVALID_ARG, "Φ.spl must be strictly increasing");
-        if (w > W) return fail(VBC_ASSERTION, "AssertionError: w <= W");
-        const int64_t R = pos[l + 1] - pos[l];
-        if (R < 0) return fail(VBC_INVALID_ARG, "pos must be non-decreasing");
-        if (ofs[l + 1] - ofs[l] != R * w) return fail(VBC_INVALID_ARG, "ofs[l+1]-ofs[l] != rows*w");
-        s.col0[l] = spl[l] - 1;
-        s.w[l] = (int32_t)w;
-        s.rbeg[l] = pos[l] - 1;
-        s.voff[l] = ofs[l] - 1;
-    }
-    s.rbeg[L] = q;
-    s.rows.resize(q);
-    for (int64_t r = 0; r < q; r++) {
-        if (idx[r] < 1 || idx[r] > m) return fail(VBC_INVALID_ARG, "idx out of range 1:m");
-        s.rows[r] = (int32_t)(idx[r] - 1);
-    }
-    in.nval = ofs[L] - 1;
-    in.K = 0;
-    in.nblocks = q;
-    return VBC_OK;
-}
-
-
-// `narrow`: the narrow-storage bits as the *_ex creates checked them (they take them out of `flags`); the plain
-// creates pass 0 and refuse both bits.
-static int create_1d(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
-                     const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                     int64_t nval, int dtype, int device, unsigned flags, unsigned narrow)
-{
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
-    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
-    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
-    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
-    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
-        sv = v ? v : val;
-        return stripes_1d(m, n, W, L, spl, pos, idx, ofs, sv, nval, in);
-    });
-}
-
-int vbc1d_create(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const int64_t *spl,
-                 const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                 int64_t nval, int dtype, int device, unsigned flags)
-{
-    return create_1d(out, m, n, W, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, 0);
-}
-
-static int stripes_2d(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
-               const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-               int64_t nval, StripesInput &in)
-{
-    // SparseMatrixVBC{U,W,Tv,Ti} inner constructor checks (SparseMatrixVBCs.jl:72-79)
-    if (m < 0) return fail(VBC_INVALID_ARG, "number of rows (m) must be >= 0");
-    if (n < 0) return fail(VBC_INVALID_ARG, "number of columns (n) must be >= 0");
-    if (U <= 0) return fail(VBC_INVALID_ARG, "U must be > 0");
-    if (W <= 0) return fail(VBC_INVALID_ARG, "W must be > 0");
-    if (K < 0 || L < 0 || !pspl || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad partition arrays");
-    if (pspl[0] != 1 || pspl[K] != m + 1) return fail(VBC_INVALID_ARG, "Π.spl must run from 1 to m+1");
-    if (spl[0] != 1 || spl[L] != n + 1) return fail(VBC_INVALID_ARG, "Φ.spl must run from 1 to n+1");
-    if (pos[0] != 1 || ofs[0] != 1) return fail(VBC_INVALID_ARG, "pos[1] and ofs[1] must be 1");
-    for (int64_t k = 0; k < K; k++) {
-        const int64_t u = pspl[k + 1] - pspl[k];
-        if (u < 1) return fail(VBC_INVALID_ARG, "Π.spl must be strictly increasing");
-        if (u > U) return fail(VBC_ASSERTION, "AssertionError: u <= U");
-    }
-    if (ofs[L] - 1 > nval) return fail(VBC_INVALID_ARG, "val shorter than ofs[L+1]-1");
-    const int64_t q = pos[L] - 1;
-    if (q < 0 || (q > 0 && !idx)) return fail(VBC_INVALID_ARG, "bad pos");
-    for (int64_t l = 0; l < L; l++)  // every stripe's blocks lie inside idx[0 .. q-1]
-        if (pos[l + 1] < pos[l] || pos[l] < 1 || pos[l + 1] - 1 > q)
-            return fail(VBC_INVALID_ARG, "pos must be non-decreasing within 1:pos[L+1]");
-    for (int64_t l = 0; l < L; l++)
-        if (ofs[l + 1] < ofs[l]) return fail(VBC_INVALID_ARG, "ofs must be non-decreasing");
-    if (ofs[L] - 1 > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
-    Stripes &s = in.s;
-    s = Stripes{};
-    s.m = m; s.n = n; s.L = L;
-    s.col0.resize(L); s.w.resize(L); s.rbeg.resize(L + 1); s.voff.resize(L);
-    // Expand every u×w tile into u stored rows with explicit x-row indices: the tile is already
-    // u row-major w-wide rows (constructors_VBC.jl:95-105), so val is used as is.
-    int64_t rows = 0;
-    for (int64_t l = 0; l < L; l++) {
-        const int64_t w = spl[l + 1] - spl[l];
-        if (w < 1) return fail(VBC_INVALID_ARG, "Φ.spl must be strictly increasing");
-        if (w > W) return fail(VBC_ASSERTION, "AssertionError: w <= W");
-        int64_t R = 0;
-        for (int64_t Q = pos[l] - 1; Q < pos[l + 1] - 1; Q++) {
-            const int64_t k = idx[Q];
-            if (k < 1 || k > K) return fail(VBC_INVALID_ARG, "idx (block row) out of range 1:K");
-            R += pspl[k] - pspl[k - 1];
-        }
-        if (ofs[l + 1] - ofs[l] != R * w) return fail(VBC_INVALID_ARG, "ofs[l+1]-ofs[l] != Σu*w");
-        s.col0[l] = spl[l] - 1;
-        s.w[l] = (int32_t)w;
-        s.rbeg[l] = rows;
-        s.voff[l] = ofs[l] - 1;
-        rows += R;
-    }
-    s.rbeg[L] = rows;
-    s.rows.resize(rows);
-    int64_t r = 0;
-    for (int64_t Q = 0; Q < q; Q++) {
-        const int64_t k = idx[Q];
-        for (int64_t i = pspl[k - 1] - 1; i < pspl[k] - 1; i++) s.rows[r++] = (int32_t)i;
-    }
-    s.grp.resize(K + 1);
-    for (int64_t k = 0; k <= K; k++) s.grp[k] = pspl[k] - 1;
-    in.nval = ofs[L] - 1;
-    in.K = K;
-    in.nblocks = q;
-    return VBC_OK;
-}
-
-static int create_2d(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
-                     const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
-                     const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
-                     int device, unsigned flags, unsigned narrow)
-{
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
-    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
-    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
-    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
-    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
-        sv = v ? v : val;
-        return stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, sv, nval, in);
-    });
-}
-
-int vbc2d_create(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K,
-                 const int64_t *pspl, int64_t L, const int64_t *spl, const int64_t *pos,
-                 const int64_t *idx, const int64_t *ofs, const void *val, int64_t nval, int dtype,
-                 int device, unsigned flags)
-{
-    return create_2d(out, m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, dtype, device, flags, 0);
-}
-
-// A SparseMatrixCSC as stripes.  bv: the values of the blocked stripes (sv then points into it).
-static int stripes_csc(int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const void *nzval,
-                       int dtype, StripesInput &in, std::vector<char> &bv, const void *&sv)
-{
-    if (m < 0 || n < 0) return fail(VBC_INVALID_ARG, "number of rows/columns must be >= 0");
-    if (!colptr || colptr[0] != 1) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
-    Stripes &s = in.s;
-    s = Stripes{};
-    s.m = m; s.n = n; s.L = n;
-    s.col0.resize(n); s.w.assign(n, 1); s.rbeg.resize(n + 1); s.voff.resize(n);
-    for (int64_t j = 0; j < n; j++) {
-        if (colptr[j + 1] < colptr[j]) return fail(VBC_INVALID_ARG, "colptr must be non-decreasing");
-        s.col0[j] = j;
-        s.rbeg[j] = colptr[j] - 1;
-        s.voff[j] = colptr[j] - 1;
-    }
-    const int64_t nnz = colptr[n] - 1;
-    if (nnz > 0 && (!rowval || !nzval)) return fail(VBC_INVALID_ARG, "NULL rowval or nzval");
-    s.rbeg[n] = nnz;
-    s.rows.resize(nnz);
-    for (int64_t p = 0; p < nnz; p++) {
-        if (rowval[p] < 1 || rowval[p] > m) return fail(VBC_INVALID_ARG, "rowval out of range 1:m");
-        s.rows[p] = (int32_t)(rowval[p] - 1);
-    }
-    // Column blocking: runs of up to 8 consecutive columns with identical row patterns (the dof
-    // columns of a node in a stiffness matrix) become one w-wide stripe, so TrSpMV! runs the blocked
-    // kernels (planar with row runs for 3-dof operators).  Each output y[j] still sums its column in
-    // stored row order (TrSpMV.jl:10-16), so the result is that of the unit-width layout, bit for bit.
-    // VBC_CSC_BLOCK=0 keeps unit stripes.
-    const char *eb = layout_knob("VBC_CSC_BLOCK");
-    if (!(eb && atoi(eb) == 0) && n > 1 && (dtype == VBC_F64 || dtype == VBC_F32 || dtype == VBC_I64)) {
-        std::vector<int64_t> g0;  // first column of each group
-        for (int64_t j = 0; j < n;) {
-            int64_t e = j + 1;
-            const int64_t len = colptr[j + 1] - colptr[j];
-            while (e < n && e - j < 8 && colptr[e + 1] - colptr[e] == len &&
-                   std::equal(rowval + colptr[j] - 1, rowval + colptr[j + 1] - 1, rowval + colptr[e] - 1))
-                e++;
-            g0.push_back(j);
-            j = e;
-        }
-        if ((int64_t)g0.size() < n) {
-            const int64_t L = (int64_t)g0.size();
-            const int esz = elem_size(dtype);
-            Stripes b;
-            b.m = m; b.n = n; b.L = L;
-            b.col0.resize(L); b.w.resize(L); b.rbeg.resize(L + 1); b.voff.resize(L);
-            bv.assign((size_t)std::max<int64_t>(nnz, 1) * esz, 0);
-            const char *src = static_cast<const char *>(nzval);
-            int64_t q = 0;
-            for (int64_t l = 0; l < L; l++) {
-                const int64_t j = g0[l], w = (l + 1 < L ? g0[l + 1] : n) - j, R = colptr[j + 1] - colptr[j];
-                b.col0[l] = j;
-                b.w[l] = (int32_t)w;
-                b.rbeg[l] = q;
-                q += R;
-            }
-            b.rbeg[L] = q;
-            b.rows.resize(q);
-            int64_t v = 0;
-            for (int64_t l = 0; l < L; l++) {
-                const int64_t j = g0[l], w = b.w[l], R = colptr[j + 1] - colptr[j];
-                b.voff[l] = v;
-                for (int64_t r = 0; r < R; r++) {
-                    b.rows[b.rbeg[l] + r] = (int32_t)(rowval[colptr[j] - 1 + r] - 1);
-                    for (int64_t c = 0; c < w; c++)
-                        std::memcpy(bv.data() + (v + r * w + c) * esz, src + (colptr[j + c] - 1 + r) * esz, (size_t)esz);
-                }
-                v += R * w;
-            }
-            in.s = std::move(b);
-            in.nval = nnz;
-            in.K = 0;
-            in.nblocks = q;
-            sv = bv.data();
-            return VBC_OK;
-        }
-    }
-    in.nval = nnz;
-    in.K = 0;
-    in.nblocks = nnz;
-    sv = nzval;
-    return VBC_OK;
-}
-
-static int create_csc(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval,
-                      const void *nzval, int dtype, int device, unsigned flags, unsigned narrow)
-{
-    if (flags & VBC_CREATE_UPDATABLE_SHARDS) return refuse_sharded_flag(out);
-    if (flags & VBC_CREATE_NARROW_SWEPT) return refuse_narrow_flag(out, kNarrowSweptPlain);
-    if (flags & VBC_CREATE_NARROW_STREAMS) return refuse_narrow_flag(out, kNarrowStreamsPlain);
-    if (flags & VBC_CREATE_NARROW_UPDATABLE) return refuse_narrow_flag(out, kNarrowUpdPlain);
-    if (flags & kNarrowBits) return refuse_narrow_flag(out, kNarrowPlain);
-    std::vector<char> bv;
-    // (the tags of an updatable create go into an nzval-shaped array, before the column blocking copies them)
-    return create_handle(out, dtype, device, flags, narrow, [&](const void *v, StripesInput &in, const void *&sv) {
-        return stripes_csc(m, n, colptr, rowval, v ? v : nzval, dtype, in, bv, sv);
-    });
-}
-
-int vbc_csc_create(vbc_handle **out, int64_t m, int64_t n, const int64_t *colptr,
-                   const int64_t *rowval, const void *nzval, int dtype, int device, unsigned flags)
-{
-    return create_csc(out, m, n, colptr, rowval, nzval, dtype, device, flags, 0);
-}
-
-int vbcx_plan_image(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
-                               const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs,
-                               const void *val, int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts,
-                               void *image, size_t capacity, size_t *bytes)
-{
-    if (!facts || !bytes) return fail(VBC_INVALID_ARG, "facts and bytes must not be NULL");
-    StripesInput in;
-    if (int st = pspl ? stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, val, nval, in)
-                      : stripes_1d(m, n, W, L, spl, pos, idx, ofs, val, nval, in))
-        return st;
-    if (flags & (VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS))
-        return fail(VBC_INVALID_ARG, "vbcx_plan_image plans one layout: VBC_CREATE_UPDATABLE(_SHARDS) do not change it");
-    if ((flags & VBC_CREATE_NARROW_UPDATABLE) && !(flags & VBC_CREATE_NARROW_VALUES))
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
-    flags &= ~VBC_CREATE_NARROW_UPDATABLE;  // (it changes no layout)
-    const unsigned narrow = flags & kNarrowBits;
-    if ((narrow & VBC_CREATE_NARROW_SWEPT) && !(narrow & VBC_CREATE_NARROW_VALUES)) return fail(VBC_INVALID_ARG, kNarrowSweptAlone);
-    if ((narrow & VBC_CREATE_NARROW_SWEPT) && dtype != VBC_F64)
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs a Float64 handle");
-    if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
-        return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
-    if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
-    if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
-    if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
-    flags &= ~kNarrowBits;
-    Plan P;
-    if (int st = plan_layout(make_config(dtype, flags, narrow, *facts), in.s, static_cast<const char *>(val), in.nval,
-                             flags, P, nullptr))
-        return st;
-    *bytes = P.ar.host.size();
-    if (!image) return VBC_OK;
-    if (capacity < *bytes) return fail(VBC_INVALID_ARG, "image buffer smaller than the arena image");
-    std::memcpy(image, P.ar.host.data(), *bytes);
-    return VBC_OK;
-}
-
-static_assert(sizeof(vbcx_map_chunk) == sizeof(UpdChunk) && offsetof(vbcx_map_chunk, vsz) == offsetof(UpdChunk, vsz) &&
-                  offsetof(vbcx_map_chunk, map) == offsetof(UpdChunk, map) && offsetof(vbcx_map_chunk, n) == offsetof(UpdChunk, n),
-              "vbc_host.h vbcx_map_chunk is vbc_handle.h UpdChunk");
-static_assert(VBCX_MAP_ZERO == kUpdZero && VBCX_MAP_SKIP == kUpdSkip && VBCX_MAP_CANON == kUpdCanon, "vbc_host.h map entries");
-
-int vbcx_value_map(int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const int64_t *pspl, int64_t L,
-                   const int64_t *spl, const int64_t *pos, const int64_t *idx, const int64_t *ofs, const void *val,
-                   int64_t nval, int dtype, unsigned flags, const vbcx_facts *facts, uint32_t *map, int64_t map_capacity,
-                   int64_t *nentries, vbcx_map_chunk *chunks, int64_t chunk_capacity, int64_t *nchunks)
-{
-    if (!facts || !nentries || !nchunks) return fail(VBC_INVALID_ARG, "facts, nentries and nchunks must not be NULL");
-    auto stripes = [&](const void *v, StripesInput &in, const void *&sv) {
-        sv = v ? v : val;
-        return pspl ? stripes_2d(m, n, U, W, K, pspl, L, spl, pos, idx, ofs, sv, nval, in)
-                    : stripes_1d(m, n, W, L, spl, pos, idx, ofs, sv, nval, in);
-    };
-    StripesInput in;
-    const void *sv = nullptr;
-    if (int st = stripes(nullptr, in, sv)) return st;
-    flags &= ~(VBC_CREATE_UPDATABLE | VBC_CREATE_UPDATABLE_SHARDS | VBC_CREATE_NARROW_UPDATABLE);
-    const unsigned narrow = flags & kNarrowBits;
-    if ((narrow & VBC_CREATE_NARROW_SWEPT) && !(narrow & VBC_CREATE_NARROW_VALUES)) return fail(VBC_INVALID_ARG, kNarrowSweptAlone);
-    if ((narrow & VBC_CREATE_NARROW_SWEPT) && dtype != VBC_F64)
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs a Float64 handle");
-    if ((narrow & VBC_CREATE_NARROW_STREAMS) && (narrow & kNarrowBelowStreams) != kNarrowBelowStreams)
-        return fail(VBC_INVALID_ARG, kNarrowStreamsAlone);
-    if (narrow && !(narrow & VBC_CREATE_NARROW_VALUES))
-        return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
-    if ((narrow & VBC_CREATE_NARROW_PAIRS) && !(narrow & VBC_CREATE_NARROW_PLANAR)) return fail(VBC_INVALID_ARG, kNarrowPairsAlone);
-    if (narrow && dtype != VBC_F64) return fail(VBC_INVALID_ARG, "VBC_CREATE_NARROW_VALUES needs a Float64 handle");
-    flags &= ~kNarrowBits;
-    const LayoutConfig cfg = make_config(dtype, flags, narrow, *facts);
-    size_t arena_used = 0;
-    bool ft_narrow = false;
-    {
-        Plan P;
-        if (int st = plan_layout(cfg, in.s, static_cast<const char *>(val), in.nval, flags, P, nullptr)) return st;
-        arena_used = P.ar.host.size();
-        ft_narrow = P.st.ft_narrow;
-    }
-    std::vector<uint32_t> mp;
-    std::vector<UpdChunk> ch;
-    if (int st = plan_value_map(cfg, flags, in, stripes, ft_narrow, arena_used, mp, ch)) return st;
-    *nentries = (int64_t)mp.size();
-    *nchunks = (int64_t)ch.size();
-    if (map && map_capacity >= *nentries && !mp.empty()) std::memcpy(map, mp.data(), mp.size() * 4);
-    if (chunks && chunk_capacity >= *nchunks && !ch.empty()) std::memcpy(chunks, ch.data(), ch.size() * sizeof(UpdChunk));
-    return VBC_OK;
 }
 
 int vbc_destroy(vbc_handle *h)
@@ -4037,164 +3395,8 @@ int vbc_mul_mat(vbc_handle *h, int trans, int64_t nrhs, const void *X, int64_t l
 }
 
 // ---------------------------------------------------------------------------------------------
-// Generic eltypes and index widths (vbc_types), strided operands
+// Generic eltypes (vbc_types), strided operands
 // ---------------------------------------------------------------------------------------------
-
-extern "C++" {  // helpers of the typed entry points (templates need C++ linkage)
-static bool is_float(int dt) { return dt == VBC_F64 || dt == VBC_F32; }
-static bool known_dtype(int dt) { return dt >= VBC_F64 && dt <= VBC_BOOL; }
-
-// Values converted to the compute eltype (empty when no conversion is needed: use `val` as is).
-static int convert_values(const void *val, int64_t nval, const vbc_types *t, std::vector<char> &out)
-{
-    if (t->val_dtype == t->compute_dtype) return VBC_OK;
-    if (nval > 0 && !val) return fail(VBC_INVALID_ARG, "NULL val");
-    out.resize((size_t)std::max<int64_t>(nval, 1) * elem_size(t->compute_dtype));
-    if (t->compute_dtype == VBC_F64) host_convert(val, t->val_dtype, nval, 1, reinterpret_cast<double *>(out.data()));
-    else if (t->compute_dtype == VBC_F32) host_convert(val, t->val_dtype, nval, 1, reinterpret_cast<float *>(out.data()));
-    else host_convert(val, t->val_dtype, nval, 1, reinterpret_cast<int64_t *>(out.data()));
-    return VBC_OK;
-}
-
-// VBC_CREATE_NARROW_VALUES on an *_ex create: checked before any device work; the flag is then taken out of
-// `flags` and handed on as the creates' `narrow` argument.
-static int check_narrow(vbc_handle **out, const vbc_types *t, unsigned &flags, unsigned &narrow)
-{
-    narrow = 0;
-    const bool upd = (flags & VBC_CREATE_NARROW_UPDATABLE) != 0;  // (its refusals name it)
-    if (!(flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE))) return VBC_OK;
-    if (flags & VBC_CREATE_NARROW_SWEPT) {  // (its refusals name it, whatever else is set)
-        if (!(flags & VBC_CREATE_NARROW_VALUES)) return refuse_narrow_flag(out, kNarrowSweptAlone);
-        if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
-            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) needs val_dtype VBC_F32 "
-                                           "and compute_dtype VBC_F64");
-        if (flags & VBC_CREATE_UPDATABLE)
-            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_SWEPT (with VBC_CREATE_NARROW_VALUES) cannot be combined with "
-                                           "VBC_CREATE_UPDATABLE: a narrow handle is made updatable by "
-                                           "VBC_CREATE_NARROW_UPDATABLE instead");
-    }
-    if (flags & VBC_CREATE_NARROW_STREAMS) {  // (its refusals name it too, whatever else is set)
-        if ((flags & kNarrowBelowStreams) != kNarrowBelowStreams) return refuse_narrow_flag(out, kNarrowStreamsAlone);
-        if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
-            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES) needs val_dtype VBC_F32 "
-                                           "and compute_dtype VBC_F64");
-        if (flags & VBC_CREATE_UPDATABLE)
-            return refuse_narrow_flag(out, "VBC_CREATE_NARROW_STREAMS (with VBC_CREATE_NARROW_VALUES) cannot be combined with "
-                                           "VBC_CREATE_UPDATABLE: a narrow handle is made updatable by "
-                                           "VBC_CREATE_NARROW_UPDATABLE instead");
-    }
-    if (upd && !(flags & VBC_CREATE_NARROW_VALUES))
-        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_UPDATABLE is valid only together with VBC_CREATE_NARROW_VALUES");
-    if ((flags & VBC_CREATE_NARROW_PAIRS) && (flags & (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR)) !=
-                                                 (VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_PLANAR))
-        return refuse_narrow_flag(out, kNarrowPairsAlone);
-    if (!(flags & VBC_CREATE_NARROW_VALUES))
-        return refuse_narrow_flag(out, "VBC_CREATE_NARROW_PLANAR is valid only together with VBC_CREATE_NARROW_VALUES");
-    if (t->val_dtype != VBC_F32 || t->compute_dtype != VBC_F64)
-        return refuse_narrow_flag(out, upd ? "VBC_CREATE_NARROW_UPDATABLE with VBC_CREATE_NARROW_VALUES needs val_dtype "
-                                             "VBC_F32 and compute_dtype VBC_F64"
-                                           : "VBC_CREATE_NARROW_VALUES needs val_dtype VBC_F32 and compute_dtype VBC_F64");
-    if (flags & VBC_CREATE_UPDATABLE)
-        return refuse_narrow_flag(out, upd ? "VBC_CREATE_NARROW_UPDATABLE cannot be combined with VBC_CREATE_UPDATABLE: "
-                                             "pass VBC_CREATE_NARROW_VALUES | VBC_CREATE_NARROW_UPDATABLE alone"
-                                           : "VBC_CREATE_NARROW_VALUES cannot be combined with VBC_CREATE_UPDATABLE (the update "
-                                             "kernel writes values of the compute eltype; a narrow handle is made "
-                                             "updatable by VBC_CREATE_NARROW_UPDATABLE instead)");
-    narrow = flags & (kNarrowBits | VBC_CREATE_NARROW_UPDATABLE);
-    flags &= ~(kNarrowBits | VBC_CREATE_NARROW_UPDATABLE);
-    return VBC_OK;
-}
-
-static int check_types(const vbc_types *t)
-{
-    if (!t) return fail(VBC_INVALID_ARG, "NULL vbc_types");
-    if (t->reserved != 0) return fail(VBC_INVALID_ARG, "vbc_types.reserved must be 0");
-    if (t->index_bits != 32 && t->index_bits != 64) return fail(VBC_INVALID_ARG, "index_bits must be 32 or 64");
-    if (!known_dtype(t->val_dtype)) return fail(VBC_UNSUPPORTED_DTYPE, "unknown val_dtype");
-    if (t->compute_dtype != VBC_F64 && t->compute_dtype != VBC_F32 && t->compute_dtype != VBC_I64)
-        return fail(VBC_UNSUPPORTED_DTYPE, "compute_dtype must be VBC_F64, VBC_F32 or VBC_I64");
-    if (t->compute_dtype == VBC_I64 && is_float(t->val_dtype))
-        return fail(VBC_UNSUPPORTED_DTYPE, "floating-point values on an integer handle (InexactError)");
-    return VBC_OK;
-}
-
-// Index array as Int64 (a copy only for Ti = Int32).
-struct Idx64 {
-    std::vector<int64_t> buf;
-    const int64_t *p = nullptr;
-    void set(const void *src, int bits, int64_t n)
-    {
-        if (!src || bits == 64) {
-            p = static_cast<const int64_t *>(src);
-            return;
-        }
-        const int32_t *s32 = static_cast<const int32_t *>(src);
-        buf.assign(s32, s32 + std::max<int64_t>(n, 0));
-        p = buf.data();
-    }
-};
-
-}  // extern "C++"
-
-int vbc1d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t W, int64_t L, const void *spl, const void *pos,
-                    const void *idx, const void *ofs, const void *val, int64_t nval, const vbc_types *t, int device,
-                    unsigned flags)
-{
-    if (int st = check_types(t)) return st;
-    unsigned narrow;
-    if (int st = check_narrow(out, t, flags, narrow)) return st;
-    if (L < 0 || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad stripe arrays");
-    Idx64 S, P, I, O;
-    S.set(spl, t->index_bits, L + 1);
-    P.set(pos, t->index_bits, L + 1);
-    O.set(ofs, t->index_bits, L + 1);
-    const int64_t q = P.p[L] - 1;
-    if (q < 0 || (q > 0 && !idx)) return fail(VBC_INVALID_ARG, "bad pos");
-    I.set(idx, t->index_bits, q);
-    std::vector<char> cv;
-    if (int st = convert_values(val, nval, t, cv)) return st;
-    return create_1d(out, m, n, W, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval, t->compute_dtype,
-                     device, flags, narrow);
-}
-
-int vbc2d_create_ex(vbc_handle **out, int64_t m, int64_t n, int64_t U, int64_t W, int64_t K, const void *pspl,
-                    int64_t L, const void *spl, const void *pos, const void *idx, const void *ofs, const void *val,
-                    int64_t nval, const vbc_types *t, int device, unsigned flags)
-{
-    if (int st = check_types(t)) return st;
-    unsigned narrow;
-    if (int st = check_narrow(out, t, flags, narrow)) return st;
-    if (K < 0 || L < 0 || !pspl || !spl || !pos || !ofs) return fail(VBC_INVALID_ARG, "bad partition arrays");
-    Idx64 PS, S, P, I, O;
-    PS.set(pspl, t->index_bits, K + 1);
-    S.set(spl, t->index_bits, L + 1);
-    P.set(pos, t->index_bits, L + 1);
-    O.set(ofs, t->index_bits, L + 1);
-    const int64_t q = P.p[L] - 1;
-    if (q < 0 || (q > 0 && !idx)) return fail(VBC_INVALID_ARG, "bad pos");
-    I.set(idx, t->index_bits, q);
-    std::vector<char> cv;
-    if (int st = convert_values(val, nval, t, cv)) return st;
-    return create_2d(out, m, n, U, W, K, PS.p, L, S.p, P.p, I.p, O.p, cv.empty() ? val : cv.data(), nval,
-                     t->compute_dtype, device, flags, narrow);
-}
-
-int vbc_csc_create_ex(vbc_handle **out, int64_t m, int64_t n, const void *colptr, const void *rowval,
-                      const void *nzval, const vbc_types *t, int device, unsigned flags)
-{
-    if (int st = check_types(t)) return st;
-    unsigned narrow;
-    if (int st = check_narrow(out, t, flags, narrow)) return st;
-    if (n < 0 || !colptr) return fail(VBC_INVALID_ARG, "colptr[1] must be 1");
-    Idx64 CP, RV;
-    CP.set(colptr, t->index_bits, n + 1);
-    const int64_t nnz = CP.p[n] - 1;
-    if (nnz < 0) return fail(VBC_INVALID_ARG, "bad colptr");
-    RV.set(rowval, t->index_bits, nnz);
-    std::vector<char> cv;
-    if (int st = convert_values(nzval, nnz, t, cv)) return st;
-    return create_csc(out, m, n, CP.p, RV.p, cv.empty() ? nzval : cv.data(), t->compute_dtype, device, flags, narrow);
-}
 
 int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int64_t incx, int64_t nx, void *y, int y_dtype,
                int64_t incy, int64_t ny, double alpha, double beta, int mem, void *stream, unsigned flags)

@@ -1,6 +1,6 @@
-// Host-side handle and launch descriptors shared by libvbc's translation units (vbc_device.hip: creation -- the
-// host-only layout planner and the device part -- and the C ABI; vbc_launch.hip / vbc_panel_launch.hip: the
-// kernel launches).
+// The host-side handle, shared by libvbc's translation units: vbc_create.hip (the create entry points),
+// vbc_device.hip (the layout planner, the device part of a create and the rest of the C ABI), vbc_launch.hip /
+// vbc_panel_launch.hip (the kernel launches).  The planner's interface (vbc_plan.h) does not depend on it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "vbc_config.h"
 #include "vbc_internal.h"
 #include "vbc_kernels.h"
+#include "vbc_launch_desc.h"
 #include "vbc_panel.h"
 #include "vbc_tiles.h"
 
@@ -26,51 +27,23 @@ namespace vbc {
         }                                                                                         \
     } while (0)
 
-// One fused launch of spmv_ranges (+ its fix-up pass).
-struct Launch {
-    std::vector<Bin> bins;
-    Bin *d_bins = nullptr;
-    int total_ranges = 0;
-    int nfill = 0;
-    size_t o_fill = 0;             // arena offset of the fill list (y indices)
-    const int32_t *d_fill = nullptr;
-    std::vector<SlotBin> sbins;    // slotted buckets (vbc_slots.h), launched before the merge kernel
-    SlotBin *d_sbins = nullptr;
-    int slot_ranges = 0;
-    std::vector<SlotBin> pbins;    // planar slotted buckets (vbc_planar.h), one launch each
-    SlotBin *d_pbins = nullptr;
-    std::vector<SweepBin> wbins;   // row-swept buckets (vbc_sweep.hip, B'x only), launched first
-    SweepBin *d_wbins = nullptr;
-    int sweep_tiles = 0;
-    int sweep_tile_bytes = 0;      // LDS accumulator bytes per wave the layout was cut for
-    int sweep_diag = 0;            // VBC_SWEEP_DIAG ablation (tools/ab.py only)
-    // B'x with several independent launch groups (swept, slotted, each planar bucket, merge + fix-up:
-    // disjoint stripes of y): the groups after the first run on side streams forked from the caller's
-    // stream by an event and joined back, so small buckets overlap instead of queueing one after the
-    // other (graph capture records them as parallel branches).  Empty when one group or VBC_FORK=0.
-    // small mixed-width B'x (vbc_device.hip build_transposed): every planar split bin in ONE launch of
-    // spmv_split_multi with fuse_split waves per chunk (0: one launch per planar bin)
-    int fuse_split = 0;
-    int fuse_p = 0;  // the fused split's P as build_transposed chose it (finalize_launch builds `multi`)
-    SplitMulti multi{};
-    std::vector<double> gwork;  // matrix bytes of each launch group (launch_groups order): the heaviest is
-                                // submitted last, so the small groups are already dispatched when it fills the chip
-    std::vector<hipStream_t> fork_streams;
-    std::vector<hipEvent_t> fork_events;  // [0]: the fork, [1 + i]: side stream i done
-    void free_device();  // the bin arrays, streams and events (vbc_device.hip)
+// Restores the caller's current device on scope exit.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
 };
 
-// The panel layout of the MFMA multi-RHS transposed product (vbc_panel.h): one launch.
-struct PanelLaunch {
-    std::vector<PanelBin> bins;
-    PanelBin *d_bins = nullptr;
-    std::vector<TileBin> tbins;  // small-tile buckets (vbc_tiles.h, u, w <= 4): one launch each
-    int total_ranges = 0;
-    int nfill = 0;
-    size_t o_fill = 0;
-    const int32_t *d_fill = nullptr;
-    void free_device();
-};
+inline bool is_float(int dt) { return dt == VBC_F64 || dt == VBC_F32; }
+inline bool known_dtype(int dt) { return dt >= VBC_F64 && dt <= VBC_BOOL; }
 
 // Integer-eltype layout (vbc_generic.hip): the reference layout itself, 0-based, on the device.
 struct IntLayout {
@@ -81,20 +54,6 @@ struct IntLayout {
     const int64_t *rbeg = nullptr;        // L+1 prefix into rows
     const int64_t *voff = nullptr;        // per stripe: first value
     const int64_t *val = nullptr;         // values as Int64
-};
-
-// Host description of the input stripes, common to 1D, 2D (expanded) and CSC inputs.
-struct Stripes {
-    int64_t m = 0, n = 0, L = 0;
-    std::vector<int64_t> col0;  // 0-based first column of stripe l
-    std::vector<int32_t> w;     // width
-    std::vector<int64_t> rbeg;  // L+1 prefix into rows
-    std::vector<int32_t> rows;  // 0-based x row of each stored w-wide row
-    std::vector<int64_t> voff;  // element offset of the stripe's first value in the input val
-    std::vector<int32_t> vst;   // per stripe: elements between its stored rows' values (empty: the width;
-                                // a column piece keeps its source stripe's stride)
-    int64_t vstride(int64_t l) const { return vst.empty() ? w[l] : vst[l]; }
-    std::vector<int64_t> grp;   // 2D input: Π's block-row starts (K + 1, 0-based); empty for 1D / CSC
 };
 
 // VBC_CREATE_UPDATABLE (vbc_update.hip): the value map of a handle.  `map` holds one 32-bit entry per stored
@@ -176,6 +135,12 @@ struct vbc_handle {
 
 namespace vbc {
 
+// vbc_device.hip: the device part of a create.  gather_facts: what a create asks the current device; instantiate:
+// a handle around a plan's uploaded arena (vbc_plan.h); release: the handle and everything it holds on its device.
+struct Plan;
+int gather_facts(int device, unsigned eltypes, bool multi, DeviceFacts &f);
+int instantiate(Plan &P, const LayoutConfig &cfg, int device, vbc_handle **out);
+void release(vbc_handle *h);
 // vbc_launch.hip
 int launch_groups(const Launch &L);  // independent launch groups of a B'x launch (vbc_launch.hip)
 int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double alpha, double beta,
@@ -204,7 +169,6 @@ int mul_int(const vbc_handle *h, int trans, const void *x, void *y, double alpha
 int convert_gather(const void *src, int src_dtype, int64_t inc, void *dst, int dst_dtype, int64_t n, hipStream_t s);
 int convert_scatter(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t inc, int64_t n, hipStream_t s);
 // vbc_update.hip
-typedef std::vector<std::pair<size_t, size_t>> ByteRanges;  // ascending, disjoint byte ranges of an arena image
 int value_map_host(int esz, int64_t nval, const std::vector<char> &tagged, const std::vector<char> &zeroed,
                    const ByteRanges &canon, const ByteRanges &narrow, std::vector<uint32_t> &map,
                    std::vector<UpdChunk> &chunks);

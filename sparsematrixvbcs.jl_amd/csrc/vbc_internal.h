@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "vbc.h"
@@ -90,6 +91,8 @@ inline void host_store(const void *src, int cdt, int64_t n, void *dst, int dt, i
     }
     (void)cdt;
 }
+
+typedef std::vector<std::pair<size_t, size_t>> ByteRanges;  // ascending, disjoint byte ranges of an arena image
 
 // The value plan of a sharded handle (vbc_sharded.cpp value_plan; vbc_host.h vbcx_sharded_value_plan): which
 // elements of the whole matrix's val each shard holds.  Packed order is shard 0's values, then shard 1's, ...;

@@ -1,8 +1,8 @@
 // vbc_update_values (vbc.h VBC_CREATE_UPDATABLE): the value map of a handle and the streaming kernel that
 // rewrites every stored value slot of its arena from a new val array.
 //
-// The map is found at create time from two extra host builds of the same pattern (vbc_device.hip
-// create_updatable): one whose val holds the tag i + 1 in element i, one whose val is all zero.  The builders
+// The map is found at create time from two extra host builds of the same pattern (vbc_create.hip
+// plan_value_map): one whose val holds the tag i + 1 in element i, one whose val is all zero.  The builders
 // only ever copy values, so the arena words that differ between the two are exactly the value
 // slots and the tag names the source element.  Runs of slots, joined over short all-zero gaps (padding
 // slots), become regions; each region is widened to whole 16-byte quads and cut into chunks (vbc_handle.h
