@@ -383,10 +383,16 @@ VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int
  *   - slotted buckets of widths <= 8 (spmm_slots, from nrhs = 2 on: the matrix read once per 8
  *     right-hand sides, every column bit-identical to vbc_mul of that column; Float32-stored buckets
  *     of VBC_CREATE_NARROW_VALUES and updatable handles included; vbc_info.planar_mask bit 22).
+ * The transposed column-major product (flags without VBC_MAT_ROWMAJOR: a Julia Matrix) of a float handle
+ * runs fused from nrhs = 2 on when the B'x layout consists of slotted buckets of those forms only -- no
+ * merge bucket (spmm_slots_col: the same arena, the same bit-for-bit guarantee per column, any ldx >= nx and
+ * ldy >= ny; vbc_info.planar_mask bit 23).  It is enqueued on `stream` alone, allocates nothing and uses no
+ * buffer of the handle: it may be captured on first use and is never ordered against other products.
  * A layout with a planar or a row-swept bucket or a bucket wider than 8, an integer handle,
- * column-major operands, the forward direction, nrhs = 1 on a slotted layout and a handle created under
- * the layout knob VBC_MM_SLOTS=0 (slotted layouts only; clears bit 22) run one SpMV per column, the
- * row-major ones through two or three strided copies per column.
+ * column-major operands on a layout with a merge bucket, the forward direction, nrhs = 1 on a slotted
+ * layout and a handle created under the layout knob VBC_MM_SLOTS=0 (slotted layouts only; clears bits 22
+ * and 23; VBC_MM_SLOTS_COL=0 clears bit 23 alone) run one SpMV per column, the row-major ones through two
+ * or three strided copies per column.
  * The column temporaries of that row-major per-column path and the carry buffer of spmm_ranges are
  * allocated by the handle's first product on the path: on a capturing `stream` that product returns
  * VBC_INVALID_ARG before it allocates anything and the capture stays valid, so run the product once
@@ -563,7 +569,10 @@ typedef struct vbc_info {
                                bit 21: some forward row-swept bucket does; bit 22: the B'x layout has a
                                slotted bucket and the row-major transposed vbc_mul_mat of this handle runs fused
                                over it (spmm_slots: the matrix read once per 8 right-hand sides); decided at
-                               create, clear under VBC_MM_SLOTS=0 and for the layouts vbc_mul_mat lists */
+                               create, clear under VBC_MM_SLOTS=0 and for the layouts vbc_mul_mat lists; bit 23:
+                               the column-major transposed vbc_mul_mat of this handle runs fused over its slotted
+                               buckets (spmm_slots_col: bit 22's conditions and no merge bucket in the B'x
+                               launch); decided at create, clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0 */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

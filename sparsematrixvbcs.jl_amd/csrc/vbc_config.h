@@ -59,6 +59,8 @@ struct LayoutConfig {
     int slot_u = 0;                   // rows per step of the slotted kernel (VBC_SLOT_U)
     bool slot_dedup = true;           // VBC_SLOT_DEDUP=0: one stored delta pattern per compressed row
     bool mm_slots = true;             // VBC_MM_SLOTS=0: row-major B'X of a slotted layout runs per column (no spmm_slots)
+    bool mm_slots_col = true;         // VBC_MM_SLOTS_COL=0: column-major B'X of a slotted layout runs per column (no
+                                      // spmm_slots_col); VBC_MM_SLOTS=0 turns this off too
     int slot_keys16 = 1;              // VBC_SLOT_KEYS16: 0 keep 32-bit keys, 1 auto, 2 compress whenever possible
     int fork = 1;                     // VBC_FORK=0: B'x launch groups queue on the caller's stream (Launch::fork_*)
     int slot_stage = -1;              // VBC_SLOT_STAGE = 0 / 4 / 8: chunks staged in LDS per y write (-1 auto)

@@ -3167,6 +3167,8 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     bool mm_slotted = false;
     if (mulmat_fuses(h, &mm_slotted) && mm_slotted)
         info->planar_mask |= 1 << 22;  // row-major B'X runs fused over the slotted buckets (spmm_slots)
+    if (mulmat_fuses_col(h))
+        info->planar_mask |= 1 << 23;  // column-major B'X runs fused over the slotted buckets (spmm_slots_col)
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3294,8 +3296,9 @@ static bool copy2d(void *dst, size_t dpitch, const void *src, size_t spitch, siz
 }
 
 // The path of a multi-RHS product on device operands: the one dispatch of mul_mat_device, and what vbc_mul_mat
-// orders (only kMatColumnTemps touches the handle's staging buffers; kMatFused's carries set has_scratch).
-enum MatPath { kMatPanels, kMatFused, kMatColumns, kMatColumnTemps };
+// orders (only kMatColumnTemps touches the handle's staging buffers; kMatFused's carries set has_scratch;
+// kMatFusedCol holds no shared state and stays on the caller's stream).
+enum MatPath { kMatPanels, kMatFused, kMatFusedCol, kMatColumns, kMatColumnTemps };
 static MatPath mat_path(const vbc_handle *h, int trans, int64_t nrhs, bool rowmajor)
 {
     if (trans ? (h->has_m && nrhs > 0 && h->n > 0) : (h->has_mf && nrhs > 0 && h->m > 0)) return kMatPanels;
@@ -3304,6 +3307,8 @@ static MatPath mat_path(const vbc_handle *h, int trans, int64_t nrhs, bool rowma
     bool fused = rowmajor && trans && nrhs > 0 && mulmat_fuses(h, &slotted);
     if (slotted && nrhs < kMmSlotsMinRhs) fused = false;
     if (fused) return kMatFused;
+    // column-major: the slotted layout alone, from kMmSlotsColMinRhs columns on (spmm_slots_col)
+    if (!rowmajor && trans && nrhs >= kMmSlotsColMinRhs && mulmat_fuses_col(h)) return kMatFusedCol;
     return rowmajor ? kMatColumnTemps : kMatColumns;
 }
 
@@ -3320,6 +3325,7 @@ static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX
         return mulmat_panel_any(h, trans, nrhs, dX, sxr, sxc, dY, syr, syc, alpha, beta, s);
     }
     if (path == kMatFused) return mulmat_rowmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
+    if (path == kMatFusedCol) return mulmat_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
     if (path == kMatColumns) {
         for (int64_t r = 0; r < nrhs && st == VBC_OK; r++)
             st = mul_dispatch(h, trans, dX + r * ldx * esz, dY + r * ldy * esz, alpha, beta, s);

@@ -150,6 +150,16 @@ int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double 
 // dispatch (vbc_mul_mat) and of vbc_info.planar_mask bit 22 (*slotted: the layout has a slotted bucket).
 bool mulmat_fuses(const vbc_handle *h, bool *slotted);
 constexpr int64_t kMmSlotsMinRhs = 2;  // smallest nrhs the slotted part runs fused at (profiles/mm_slots_time.json)
+// Column-major B'X with nrhs >= kMmSlotsColMinRhs columns runs fused over the slotted buckets (mulmat_colmajor,
+// spmm_slots_col): mulmat_fuses's conditions for a slotted layout, no merge bucket in the launch (spmm_ranges is
+// row-major only) and VBC_MM_SLOTS_COL not 0.  The one predicate of the dispatch and of planar_mask bit 23.
+bool mulmat_fuses_col(const vbc_handle *h);
+constexpr int64_t kMmSlotsColMinRhs = 2;  // smallest nrhs the column-major form runs fused at (profiles/mm_slots_col_time.json)
+// columns per launch, 4 or 8: 8 columns as two NR = 4 launches sum to 1805.9 us over the three forms on FE-2D, as one
+// NR = 8 launch to 1833.6 us (profiles/mm_slots_col_time_cap8.json, measured on a build with 8 here)
+constexpr int64_t kMmSlotsColChunk = 4;
+int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
+                    double beta, hipStream_t s);
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
 // A cached buffer of the handle (`what`) has to grow for a product on `s`.  hipFree / hipMalloc are not stream

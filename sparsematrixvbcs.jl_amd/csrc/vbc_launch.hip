@@ -302,6 +302,48 @@ static int mulmat_slots(const vbc_handle *h, int64_t nrhs, const char *X, int64_
     return VBC_OK;
 }
 
+int launch_slots_mmc_f64(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
+                         const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
+                         double alpha, double beta, bool rd, hipStream_t stream);
+int launch_slots_mmc_f32(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
+                         const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
+                         double alpha, double beta, bool rd, hipStream_t stream);
+int launch_slots_mmc_f64n(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
+                          const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
+                          double alpha, double beta, bool rd, hipStream_t stream);
+
+bool mulmat_fuses_col(const vbc_handle *h)
+{
+    bool slotted = false;
+    if (!h->cfg.mm_slots_col || !mulmat_fuses(h, &slotted) || !slotted) return false;
+    return h->lt.bins.empty() && h->lt.total_ranges == 0;  // merge buckets: per column
+}
+
+// Column-major B'X of a slotted layout without merge buckets (spmm_slots_col, vbc_slots_mmc.h): chunks of
+// <= kMmSlotsColChunk columns one after another on the caller's stream, each followed by the fill list of its
+// columns.  Nothing allocated, no side stream, no handle buffer: capture-safe on first use, never ordered.
+int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
+                    double beta, hipStream_t s)
+{
+    const Launch &L = h->lt;
+    int wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
+    for (const SlotBin &b : L.sbins)
+        if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
+    const int vsz = L.sbins[0].vsz > 0 ? L.sbins[0].vsz : h->esz;
+    const auto fn = h->esz == 4 ? launch_slots_mmc_f32 : vsz == 4 ? launch_slots_mmc_f64n : launch_slots_mmc_f64;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmSlotsColChunk) {
+        const int nr = (int)std::min<int64_t>(kMmSlotsColChunk, nrhs - c0);
+        const hipError_t e = (hipError_t)fn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, L.sbins[0].kc != 0,
+                                            wonly, L.d_fill, L.nfill, X + c0 * ldx * h->esz, ldx, Y + c0 * ldy * h->esz,
+                                            ldy, nr, alpha, beta, beta != 0.0, s);
+        if (e != hipSuccess) {
+            set_error("spmm_slots_col launch failed: %s", hipGetErrorString(e));
+            return VBC_HIP_ERROR;
+        }
+    }
+    return VBC_OK;
+}
+
 // Multi-RHS transposed product on the tiled stream (row-major X / Y), in chunks of <= 64 columns.
 template <typename T>
 static int mulmat_t_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,

@@ -1,0 +1,5 @@
+// spmm_slots_col launchers, fp64 compute on Float32 stored values (VBC_CREATE_NARROW_VALUES).
+#define VBC_SLOTS_T double
+#define VBC_SLOTS_S float
+#define VBC_SLOTS_SUFFIX f64n
+#include "vbc_slots_mmc_launch.inc"

@@ -132,7 +132,8 @@ def mulmat_(Y, A, X, alpha=1.0, beta=0.0, *, stream=None, quirks=False, engine="
     of B for B'X, of Bᵀ for B·X -- row- or column-major operands, the matrix read once; engine="vector":
     the SpMV layout -- row-major B'X runs fused vector kernels when that layout has merge and slotted buckets of
     widths <= 8 only (a slotted bucket: the matrix read once per 8 columns, each column bit-identical to mul_;
-    info()["planar_mask"] bit 22), one SpMV per column otherwise (planar / swept buckets, column-major, B·X)."""
+    info()["planar_mask"] bit 22), column-major B'X does when it has slotted buckets of those forms only (no
+    merge bucket; the same guarantee, bit 23), one SpMV per column otherwise (planar / swept buckets, B·X)."""
     B, trans = _unwrap(A)
     mem, dev, stream = _mem_device_stream(X, Y, stream)
     cdt = _compute_for(Y, B)
