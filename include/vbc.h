@@ -388,11 +388,20 @@ VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int
  * merge bucket (spmm_slots_col: the same arena, the same bit-for-bit guarantee per column, any ldx >= nx and
  * ldy >= ny; vbc_info.planar_mask bit 23).  It is enqueued on `stream` alone, allocates nothing and uses no
  * buffer of the handle: it may be captured on first use and is never ordered against other products.
- * A layout with a planar or a row-swept bucket or a bucket wider than 8, an integer handle,
- * column-major operands on a layout with a merge bucket, the forward direction, nrhs = 1 on a slotted
- * layout and a handle created under the layout knob VBC_MM_SLOTS=0 (slotted layouts only; clears bits 22
- * and 23; VBC_MM_SLOTS_COL=0 clears bit 23 alone) run one SpMV per column, the row-major ones through two
- * or three strided copies per column.
+ * On a handle created under the layout knob VBC_MM_PLANAR_COL=1 (opt-in) the same product of a layout with planar
+ * buckets -- the 3-dof stiffness operators -- runs fused from nrhs = 2 on when every planar bucket is a plain chunk-planar or a lane-pair one of width 3..8 (one wave per range: no split
+ * bucket, no fused small-matrix split, no lane streams), the slotted buckets beside them have spmm_slots_col's
+ * forms and there is no swept and no merge bucket (spmm_planar_col / spmm_pair_col, one launch per planar bucket
+ * and chunk of 4 columns, after spmm_slots_col for the slotted buckets: each stored value loaded once per chunk,
+ * every column bit-identical to vbc_mul of that column, Float32-stored buckets of VBC_CREATE_NARROW_PLANAR /
+ * VBC_CREATE_NARROW_PAIRS and updatable handles included; vbc_info.planar_mask bit 24).  It too stays on `stream`
+ * alone, allocates nothing and may be captured on first use.
+ * A layout with a row-swept bucket or a bucket wider than 8, row-major operands on a layout with a planar
+ * bucket, split planar buckets and lane streams, an integer handle, column-major operands on a layout with a
+ * merge bucket, the forward direction, nrhs = 1 on a slotted or planar layout and a handle created under the
+ * layout knob VBC_MM_SLOTS=0 (clears bits 22, 23 and 24; VBC_MM_SLOTS_COL=0 clears bits 23 and 24; bit 24
+ * is set only under VBC_MM_PLANAR_COL=1) run one SpMV per column, the row-major ones through two or three strided
+ * copies per column.
  * The column temporaries of that row-major per-column path and the carry buffer of spmm_ranges are
  * allocated by the handle's first product on the path: on a capturing `stream` that product returns
  * VBC_INVALID_ARG before it allocates anything and the capture stays valid, so run the product once
@@ -572,7 +581,12 @@ typedef struct vbc_info {
                                create, clear under VBC_MM_SLOTS=0 and for the layouts vbc_mul_mat lists; bit 23:
                                the column-major transposed vbc_mul_mat of this handle runs fused over its slotted
                                buckets (spmm_slots_col: bit 22's conditions and no merge bucket in the B'x
-                               launch); decided at create, clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0 */
+                               launch); decided at create, clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0; bit 24:
+                               the column-major transposed vbc_mul_mat of this handle runs fused over its planar
+                               buckets (spmm_planar_col / spmm_pair_col, and spmm_slots_col for slotted buckets
+                               beside them: the layouts vbc_mul_mat lists; bits 22 and 23 stay clear on such a
+                               layout); decided at create, set only under VBC_MM_PLANAR_COL=1 (opt-in) and
+                               clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0 */
 } vbc_info;
 
 /* Writes VBC_INFO_SIZE bytes: `info` must be a vbc_info of this header's version (vbc_version() /

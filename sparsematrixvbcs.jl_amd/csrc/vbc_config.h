@@ -61,6 +61,11 @@ struct LayoutConfig {
     bool mm_slots = true;             // VBC_MM_SLOTS=0: row-major B'X of a slotted layout runs per column (no spmm_slots)
     bool mm_slots_col = true;         // VBC_MM_SLOTS_COL=0: column-major B'X of a slotted layout runs per column (no
                                       // spmm_slots_col); VBC_MM_SLOTS=0 turns this off too
+    bool mm_planar_col = false;       // VBC_MM_PLANAR_COL=1: column-major B'X of a planar layout runs fused
+                                      // (spmm_planar_col / spmm_pair_col; planar_mask bit 24).  Opt-in, although it wins
+                                      // at every nrhs measured: tests/test_gpu_planar.py asserts the
+                                      // exact planar_mask of planar handles created under the default knobs.
+                                      // VBC_MM_SLOTS=0 and VBC_MM_SLOTS_COL=0 turn it off too
     int slot_keys16 = 1;              // VBC_SLOT_KEYS16: 0 keep 32-bit keys, 1 auto, 2 compress whenever possible
     int fork = 1;                     // VBC_FORK=0: B'x launch groups queue on the caller's stream (Launch::fork_*)
     int slot_stage = -1;              // VBC_SLOT_STAGE = 0 / 4 / 8: chunks staged in LDS per y write (-1 auto)

@@ -3169,6 +3169,8 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
         info->planar_mask |= 1 << 22;  // row-major B'X runs fused over the slotted buckets (spmm_slots)
     if (mulmat_fuses_col(h))
         info->planar_mask |= 1 << 23;  // column-major B'X runs fused over the slotted buckets (spmm_slots_col)
+    if (mulmat_fuses_planar_col(h))
+        info->planar_mask |= 1 << 24;  // column-major B'X runs fused over the planar buckets (spmm_planar_col / spmm_pair_col)
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
     return VBC_OK;
 }
@@ -3309,6 +3311,8 @@ static MatPath mat_path(const vbc_handle *h, int trans, int64_t nrhs, bool rowma
     if (fused) return kMatFused;
     // column-major: the slotted layout alone, from kMmSlotsColMinRhs columns on (spmm_slots_col)
     if (!rowmajor && trans && nrhs >= kMmSlotsColMinRhs && mulmat_fuses_col(h)) return kMatFusedCol;
+    // ... or a layout with planar buckets, from kMmPlanarColMinRhs columns on (spmm_planar_col / spmm_pair_col)
+    if (!rowmajor && trans && nrhs >= kMmPlanarColMinRhs && mulmat_fuses_planar_col(h)) return kMatFusedCol;
     return rowmajor ? kMatColumnTemps : kMatColumns;
 }
 
@@ -3325,7 +3329,9 @@ static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX
         return mulmat_panel_any(h, trans, nrhs, dX, sxr, sxc, dY, syr, syc, alpha, beta, s);
     }
     if (path == kMatFused) return mulmat_rowmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
-    if (path == kMatFusedCol) return mulmat_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
+    if (path == kMatFusedCol)  // (a layout with planar buckets never passes mulmat_fuses_col)
+        return h->lt.pbins.empty() ? mulmat_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s)
+                                   : mulmat_planar_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
     if (path == kMatColumns) {
         for (int64_t r = 0; r < nrhs && st == VBC_OK; r++)
             st = mul_dispatch(h, trans, dX + r * ldx * esz, dY + r * ldy * esz, alpha, beta, s);

@@ -160,6 +160,21 @@ constexpr int64_t kMmSlotsColMinRhs = 2;  // smallest nrhs the column-major form
 constexpr int64_t kMmSlotsColChunk = 4;
 int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
+// Column-major B'X with nrhs >= kMmPlanarColMinRhs columns runs fused over a layout with planar buckets
+// (mulmat_planar_colmajor; spmm_planar_col / spmm_pair_col, and spmm_slots_col for the slotted buckets beside them):
+// a float handle, no swept or merge bucket, no fused small-matrix split, every planar bucket of kind 0 with one wave
+// per range, chunk rows (no lane streams), width 3..8, plain or lane pairs, the slotted buckets of spmm_slots_col's
+// forms, VBC_MM_PLANAR_COL=1 (opt-in) and neither VBC_MM_SLOTS nor VBC_MM_SLOTS_COL 0.  The one predicate of the dispatch and of
+// planar_mask bit 24.
+bool mulmat_fuses_planar_col(const vbc_handle *h);
+// smallest nrhs the planar column-major form runs fused at: it beats nrhs x vbc_mul by more than the spread from
+// nrhs = 2 on in fp64, fp32 and narrow on the ldoor stand-in (profiles/mm_planar_col_time.json)
+constexpr int64_t kMmPlanarColMinRhs = 2;
+// columns per launch, 2 or 4: 8 columns as two NR = 4 launches sum to 723.5 us over the three forms, as four NR = 2
+// launches to 833.5 us (the same record, `fused` against `fused_by2`)
+constexpr int64_t kMmPlanarColChunk = 4;
+int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
+                           double alpha, double beta, hipStream_t s);
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
 // A cached buffer of the handle (`what`) has to grow for a product on `s`.  hipFree / hipMalloc are not stream

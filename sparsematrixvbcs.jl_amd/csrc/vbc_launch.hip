@@ -255,6 +255,22 @@ int launch_slots_mm_f32(const SlotBin *d_bins, int nbins, int total_ranges, int 
 int launch_slots_mm_f64n(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
                          int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
 
+// The slotted bins of the B'x launch (at least one) all have a form spmm_slots / spmm_slots_col covers: kind 0, a
+// compile-time width, one segment per lane slot or the fp32 w = 2 two-segment rows; keys and stored value type
+// alike in every bin of the launch.
+static bool slots_mm_forms(const vbc_handle *h)
+{
+    const Launch &L = h->lt;
+    const SlotBin &f = L.sbins[0];
+    if (f.vsz != 0 && !(f.vsz == 4 && h->esz == 8)) return false;
+    for (const SlotBin &b : L.sbins) {
+        const bool narrow2 = h->esz == 4 && b.spl == 2 && b.wkey == 2;
+        if (b.kind != 0 || b.planar || b.wkey < 1 || b.wkey > 8 || !(b.spl == 1 || narrow2)) return false;
+        if (b.vsz != f.vsz || (b.kc != 0) != (f.kc != 0) || VBC_ABL(b.diag != 0)) return false;
+    }
+    return true;
+}
+
 bool mulmat_fuses(const vbc_handle *h, bool *slotted)
 {
     const Launch &L = h->lt;
@@ -264,17 +280,7 @@ bool mulmat_fuses(const vbc_handle *h, bool *slotted)
     for (const Bin &b : L.bins)
         if (b.wkey == 0) return false;  // runtime-width buckets: per column
     if (L.sbins.empty()) return true;   // the merge layout alone: spmm_ranges, as ever
-    if (!h->cfg.mm_slots) return false;
-    const SlotBin &f = L.sbins[0];
-    if (f.vsz != 0 && !(f.vsz == 4 && h->esz == 8)) return false;
-    for (const SlotBin &b : L.sbins) {
-        // the forms spmm_slots covers: kind 0, a compile-time width, one segment per lane slot or the fp32 w = 2
-        // two-segment rows; keys and stored value type alike in every bin of the launch
-        const bool narrow2 = h->esz == 4 && b.spl == 2 && b.wkey == 2;
-        if (b.kind != 0 || b.planar || b.wkey < 1 || b.wkey > 8 || !(b.spl == 1 || narrow2)) return false;
-        if (b.vsz != f.vsz || (b.kc != 0) != (f.kc != 0) || VBC_ABL(b.diag != 0)) return false;
-    }
-    return true;
+    return h->cfg.mm_slots && slots_mm_forms(h);
 }
 
 // The slotted bins of a row-major B'X (spmm_slots, vbc_slots_mm.h): chunks of <= 8 columns one after another on
@@ -338,6 +344,73 @@ int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ld
                                             ldy, nr, alpha, beta, beta != 0.0, s);
         if (e != hipSuccess) {
             set_error("spmm_slots_col launch failed: %s", hipGetErrorString(e));
+            return VBC_HIP_ERROR;
+        }
+    }
+    return VBC_OK;
+}
+
+int launch_planar_mmc_f64(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                          double beta, bool rd, hipStream_t stream);
+int launch_planar_mmc_f32(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                          double beta, bool rd, hipStream_t stream);
+int launch_planar_mmc_f64n(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                           double beta, bool rd, hipStream_t stream);
+
+bool mulmat_fuses_planar_col(const vbc_handle *h)
+{
+    const Launch &L = h->lt;
+    if (!h->has_t || h->n <= 0 || h->dtype == VBC_I64) return false;
+    if (!h->cfg.mm_slots || !h->cfg.mm_slots_col || !h->cfg.mm_planar_col) return false;
+    if (!L.wbins.empty() || !L.bins.empty() || L.total_ranges != 0 || L.fuse_split) return false;
+    if (L.pbins.empty()) return false;
+    for (const SlotBin &b : L.pbins) {
+        // the forms spmm_planar_col / spmm_pair_col cover: kind 0, one wave per range, chunk rows (no lane streams),
+        // widths 3..8, plain or the fp64 lane pairs; values of the compute eltype or Float32 on an fp64 handle
+        if (b.kind != 0 || !b.planar || b.split > 1 || b.fused || b.lanes || b.dot || b.holes || b.ks > 1) return false;
+        if (b.wkey < 3 || b.wkey > 8 || b.run < 1 || b.run > 3 || VBC_ABL(b.diag != 0)) return false;
+        if (b.pair && (h->esz != 8 || b.wkey != 3 || b.run != 3)) return false;
+        if (b.vsz != 0 && !(b.vsz == 4 && h->esz == 8)) return false;
+    }
+    return L.sbins.empty() || slots_mm_forms(h);
+}
+
+// Column-major B'X of a layout with planar buckets (spmm_planar_col / spmm_pair_col, vbc_planar_mmc.h): per chunk of
+// <= kMmPlanarColChunk columns the slotted bins (spmm_slots_col), then one launch per planar bin, then the fill list,
+// one after another on the caller's stream.  Nothing allocated, no side stream, no handle buffer: capture-safe on
+// first use, never ordered.
+int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
+                           double alpha, double beta, hipStream_t s)
+{
+    const Launch &L = h->lt;
+    const bool rd = beta != 0.0;
+    int wonly = -1;
+    auto sfn = h->esz == 4 ? launch_slots_mmc_f32 : launch_slots_mmc_f64;  // (the fill list alone: any unit of T)
+    if (!L.sbins.empty()) {
+        wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
+        for (const SlotBin &b : L.sbins)
+            if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
+        if (h->esz == 8 && L.sbins[0].vsz == 4) sfn = launch_slots_mmc_f64n;
+    }
+    const bool skc = !L.sbins.empty() && L.sbins[0].kc != 0;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmPlanarColChunk) {
+        const int nr = (int)std::min<int64_t>(kMmPlanarColChunk, nrhs - c0);
+        const char *xs = X + c0 * ldx * h->esz;
+        char *ys = Y + c0 * ldy * h->esz;
+        hipError_t e = hipSuccess;
+        if (L.slot_ranges > 0)
+            e = (hipError_t)sfn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, skc, wonly, nullptr, 0, xs, ldx,
+                                ys, ldy, nr, alpha, beta, rd, s);
+        for (size_t i = 0; i < L.pbins.size() && e == hipSuccess; i++) {
+            const SlotBin &pb = L.pbins[i];
+            const auto pfn = h->esz == 4 ? launch_planar_mmc_f32 : pb.vsz == 4 ? launch_planar_mmc_f64n : launch_planar_mmc_f64;
+            e = (hipError_t)pfn(pb, xs, ldx, ys, ldy, nr, alpha, beta, rd, s);
+        }
+        if (e == hipSuccess && L.nfill > 0)
+            e = (hipError_t)sfn(L.d_sbins, (int)L.sbins.size(), 0, h->cfg.xcd, skc, wonly, L.d_fill, L.nfill, xs, ldx, ys,
+                                ldy, nr, alpha, beta, rd, s);
+        if (e != hipSuccess) {
+            set_error("spmm_planar_col launch failed: %s", hipGetErrorString(e));
             return VBC_HIP_ERROR;
         }
     }

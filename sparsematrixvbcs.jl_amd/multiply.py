@@ -133,7 +133,9 @@ def mulmat_(Y, A, X, alpha=1.0, beta=0.0, *, stream=None, quirks=False, engine="
     the SpMV layout -- row-major B'X runs fused vector kernels when that layout has merge and slotted buckets of
     widths <= 8 only (a slotted bucket: the matrix read once per 8 columns, each column bit-identical to mul_;
     info()["planar_mask"] bit 22), column-major B'X does when it has slotted buckets of those forms only (no
-    merge bucket; the same guarantee, bit 23), one SpMV per column otherwise (planar / swept buckets, B·X)."""
+    merge bucket; the same guarantee, bit 23) or plain planar / lane-pair buckets of widths 3..8 beside them (no split
+    bucket, no lane streams, no swept or merge bucket; handles created under VBC_MM_PLANAR_COL=1; the same guarantee,
+    bit 24), one SpMV per column otherwise (row-major on planar buckets, lane streams, swept buckets, B·X)."""
     B, trans = _unwrap(A)
     mem, dev, stream = _mem_device_stream(X, Y, stream)
     cdt = _compute_for(Y, B)
