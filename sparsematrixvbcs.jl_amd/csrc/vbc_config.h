@@ -1,6 +1,6 @@
 // Create-time configuration of a handle: what the device reports (DeviceFacts) and every layout / tuning
 // knob with the targets derived from them (LayoutConfig).  make_config is the one place that reads the
-// environment; the layout planner (vbc_device.hip plan_layout) takes the result and reads neither the environment nor the device.
+// environment; the layout planner (vbc_plan.hip plan_layout) takes the result and reads neither the environment nor the device.
 #pragma once
 #include <cstdint>
 

@@ -1,6 +1,6 @@
 // The host-side handle, shared by libvbc's translation units: vbc_create.hip (the create entry points),
-// vbc_device.hip (the layout planner, the device part of a create and the rest of the C ABI), vbc_launch.hip /
-// vbc_panel_launch.hip (the kernel launches).  The planner's interface (vbc_plan.h) does not depend on it.
+// vbc_device.hip (the device part of a create and the rest of the C ABI), vbc_launch.hip / vbc_panel_launch.hip
+// (the kernel launches).  The layout planner (vbc_plan.h and its units vbc_plan*.hip) does not depend on it.
 #pragma once
 #include <hip/hip_runtime.h>
 

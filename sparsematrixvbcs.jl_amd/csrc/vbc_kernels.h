@@ -1,4 +1,5 @@
-// gfx950 variable-block SpMV kernels (device code, included by vbc_device.hip only).
+// gfx950 variable-block SpMV kernels (device code; the host units -- the layout planner, the device part of a
+// create, the launches -- include it for the bin descriptors and the key constants).
 //
 // Merge-based, flat streaming design.  Per width bucket w the stored w-wide rows of
 // the product are one stream of *entries*, ordered by output *segment*:
@@ -25,7 +26,7 @@
 
 #include "vbc_internal.h"  // VBC_ABL
 
-// The arrangement of a narrow lane-pair run-row (VBC_CREATE_NARROW_PAIRS; vbc_planar.h pair_load, vbc_device.hip
+// The arrangement of a narrow lane-pair run-row (VBC_CREATE_NARROW_PAIRS; vbc_planar.h pair_load, vbc_plan_bins.hip
 // put_pair_run): 0 = the wide run-row's element offsets, 1 = 16 B per lane and a tail.  A build-time choice so both
 // can be measured (make pair_form_alt builds the other one); DESIGN.md §10.3 says which is kept and why.
 #ifndef VBC_PAIR_FORM

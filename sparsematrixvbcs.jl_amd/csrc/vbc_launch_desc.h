@@ -35,7 +35,7 @@ struct Launch {
     // disjoint stripes of y): the groups after the first run on side streams forked from the caller's
     // stream by an event and joined back, so small buckets overlap instead of queueing one after the
     // other (graph capture records them as parallel branches).  Empty when one group or VBC_FORK=0.
-    // small mixed-width B'x (vbc_device.hip build_transposed): every planar split bin in ONE launch of
+    // small mixed-width B'x (vbc_plan.hip build_transposed): every planar split bin in ONE launch of
     // spmv_split_multi with fuse_split waves per chunk (0: one launch per planar bin)
     int fuse_split = 0;
     int fuse_p = 0;  // the fused split's P as build_transposed chose it (finalize_launch builds `multi`)

@@ -1,4 +1,5 @@
-// gfx950 multi-RHS transposed product on matrix cores (device code, included by vbc_device.hip).
+// gfx950 multi-RHS transposed product on matrix cores (device code; the host units include it through
+// vbc_launch_desc.h for PanelBin, which the layout planner's vbc_plan_panel.hip fills).
 //
 // Y = alpha * B' X + beta * Y for k right-hand sides (multiply_1DVBC.jl:90-134 and
 // multiply_VBC.jl:93-147 applied column by column; the reference itself has no matrix mul!,

@@ -1,7 +1,9 @@
 // The layout planner's interface: from the input stripes and a LayoutConfig to the arena image and the launch
 // descriptors without device pointers.  Pure host code: the planner calls no HIP runtime function and reads no
 // environment.  The create entry points (vbc_create.hip) make the plans; the device part of a create (instantiate)
-// uploads one.  The planner's builders still share vbc_device.hip with the device part.
+// uploads one.  The planner is three units of its own -- vbc_plan.hip (plan_layout and the per-direction planners),
+// vbc_plan_bins.hip (the per-bucket builders), vbc_plan_panel.hip (the panel layouts) -- which share
+// vbc_plan_impl.h; tests/test_plan_host.py checks that their objects reference no HIP runtime function and no getenv.
 #pragma once
 #include <algorithm>
 #include <cstdint>

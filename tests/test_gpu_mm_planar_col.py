@@ -120,7 +120,7 @@ def assert_fuses(inf, **kw):
 
 def assert_fuses_w(inf, kind, w, run, **kw):
     """assert_fuses, but for fp32 w = 4: a row is exactly one 16-B lane vector, which the planner keeps in the plain
-    slotted form whatever VBC_SLOT_PLANAR says (slot_planar(), csrc/vbc_device.hip).  There the product is
+    slotted form whatever VBC_SLOT_PLANAR says (slot_planar(), csrc/vbc_plan_bins.hip).  There the product is
     spmm_slots_col's (bit 23), and the case still compares a fused product with the per-column one."""
     if kind == "f32" and w == 4:
         assert inf["planar_bins"] == 0 and inf["slot_bins"] >= 1 and inf["bins_t"] == 0 and inf["sweep_bins"] == 0, inf

@@ -249,7 +249,7 @@ problem("tiles-heights-odd", fp32=True, multi=True)(lambda: integer_values(_vbc2
 #   fixed-w1to8, -odd: one merge bin per stored width (the per-bin carry slice and the bin lookup), 700 x 216 and
 #     701 x 217 (both extents odd);
 #   fixed-long: three 5-wide stripes of about 2100 stored rows each.  A range is one wave's share of a bin's tiles;
-#     build_bucket (csrc/vbc_device.hip) gives a bin nranges = min(round(target_ranges * its share of the entries),
+#     build_bucket (csrc/vbc_plan_bins.hip) gives a bin nranges = min(round(target_ranges * its share of the entries),
 #     (ntiles + 1) / 2) ranges of tiles_per_range = ceil(ntiles / nranges) tiles, and a tile holds rpi * tile_k
 #     entries: rpi = 64 / 5 = 12 slots of tile_k = 4 (Float64) / 8 (Float32) entries.  The 6326 entries are 132 /
 #     66 tiles; target_ranges is CUs x occupancy x 4 >= 1024 on any gfx950 part, so nranges = 66 / 33 and

@@ -7,11 +7,16 @@ planner to that layout byte for byte; tests/test_gpu_plan.py checks that the rec
 
 Recording property: planned with val all zero and with val holding the tag i + 1 in element i, the images have
 one length and differ only inside value slots -- what VBC_CREATE_UPDATABLE's value map is built from.
+
+Host-only property: the objects of the planner's translation units (csrc/vbc_plan*.hip) leave no HIP runtime
+function and no getenv undefined, i.e. they call none.
 """
 import ctypes as C
 import hashlib
 import json
 import os
+import re
+import shutil
 import subprocess
 from pathlib import Path
 
@@ -220,6 +225,31 @@ def test_tagged_and_zero_images_differ_in_value_slots_only(name, golden, monkeyp
     assert (wz[diff] == 0).all()
     assert ((wt[diff] >= 1) & (wt[diff] <= nval)).all()
     assert np.unique(wt[diff]).size == int(B.ofs[-1]) - 1  # every stored value of the matrix is somewhere
+
+
+PLANNER_OBJECTS = ("vbc_plan.o", "vbc_plan_bins.o", "vbc_plan_panel.o")
+
+
+def undefined_symbols(obj):
+    path = L.PKG_DIR / "build" / obj
+    assert path.exists(), f"{path}: the library's build leaves its objects there"
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    r = subprocess.run([nm, "-u", str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [line.split()[-1] for line in r.stdout.splitlines() if line.strip()]
+
+
+def test_planner_objects_call_no_hip_and_read_no_environment():
+    """vbc_plan.h's promise, enforced: the planner's translation units reference no HIP runtime function (hipMalloc,
+    hipMemcpy, ...: `hip` and an upper-case letter; the compiler's own __hip* registration symbols are not calls of
+    the planner's) and no getenv.  The device part's object does reference one, so the listing can see them."""
+    runtime = re.compile(r"hip[A-Z]")
+    for obj in PLANNER_OBJECTS:
+        syms = undefined_symbols(obj)
+        assert syms, obj  # (it calls at least the C++ runtime: an empty listing would be a listing that failed)
+        assert [s for s in syms if runtime.match(s)] == [], obj
+        assert [s for s in syms if s in ("getenv", "secure_getenv")] == [], obj
+    assert [s for s in undefined_symbols("vbc_device.o") if runtime.match(s)]
 
 
 SANITIZED = ("fused_f64", "slots_key16_f32", "fwd_panel_f32")
