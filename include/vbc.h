@@ -396,12 +396,21 @@ VBC_API int vbc_mul_ex(vbc_handle *h, int trans, const void *x, int x_dtype, int
  * every column bit-identical to vbc_mul of that column, Float32-stored buckets of VBC_CREATE_NARROW_PLANAR /
  * VBC_CREATE_NARROW_PAIRS and updatable handles included; vbc_info.planar_mask bit 24).  It too stays on `stream`
  * alone, allocates nothing and may be captured on first use.
+ * The forward column-major product (trans = 0, flags without VBC_MAT_ROWMAJOR) of a float handle without
+ * VBC_CREATE_MULTI_FORWARD panels, created under the layout knob VBC_MM_FWD_COL=1 (opt-in), runs fused from nrhs = 2
+ * on when the forward product is one launch on B's own layout (not on C = Bᵀ, one width bucket) whose buckets are all
+ * forward row runs (blocks of R = 2 or 3 output rows by w = 2, 3 or 4 columns, one wave per range: no split bucket,
+ * no lane streams) or fp64 forward lane pairs (3 x 3 node blocks), with no slotted, swept or merge bucket
+ * (spmm_planar_fwd_col / spmm_pair_col with DOT, one launch per bucket and chunk of 4 columns, then the rows without
+ * entries: each stored value loaded once per chunk, every column bit-identical to vbc_mul of that column,
+ * Float32-stored buckets of VBC_CREATE_NARROW_PLANAR / VBC_CREATE_NARROW_PAIRS and updatable handles included;
+ * vbc_info.planar_mask bit 25).  It too stays on `stream` alone, allocates nothing and may be captured on first use.
  * A layout with a row-swept bucket or a bucket wider than 8, row-major operands on a layout with a planar
  * bucket, split planar buckets and lane streams, an integer handle, column-major operands on a layout with a
- * merge bucket, the forward direction, nrhs = 1 on a slotted or planar layout and a handle created under the
- * layout knob VBC_MM_SLOTS=0 (clears bits 22, 23 and 24; VBC_MM_SLOTS_COL=0 clears bits 23 and 24; bit 24
- * is set only under VBC_MM_PLANAR_COL=1) run one SpMV per column, the row-major ones through two or three strided
- * copies per column.
+ * merge bucket, every other forward product, nrhs = 1 on a slotted or planar layout and a handle created under the
+ * layout knob VBC_MM_SLOTS=0 (clears bits 22 to 25; VBC_MM_SLOTS_COL=0 clears bits 23 to 25; bit 24
+ * is set only under VBC_MM_PLANAR_COL=1, bit 25 only under VBC_MM_FWD_COL=1) run one SpMV per column, the row-major
+ * ones through two or three strided copies per column.
  * The column temporaries of that row-major per-column path and the carry buffer of spmm_ranges are
  * allocated by the handle's first product on the path: on a capturing `stream` that product returns
  * VBC_INVALID_ARG before it allocates anything and the capture stays valid, so run the product once
@@ -586,6 +595,10 @@ typedef struct vbc_info {
                                buckets (spmm_planar_col / spmm_pair_col, and spmm_slots_col for slotted buckets
                                beside them: the layouts vbc_mul_mat lists; bits 22 and 23 stay clear on such a
                                layout); decided at create, set only under VBC_MM_PLANAR_COL=1 (opt-in) and
+                               clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0; bit 25: the column-major forward
+                               vbc_mul_mat (trans = 0) of this handle runs fused over its forward row runs or
+                               forward lane pairs (spmm_planar_fwd_col / spmm_pair_col with DOT: the layouts
+                               vbc_mul_mat lists); decided at create, set only under VBC_MM_FWD_COL=1 (opt-in) and
                                clear under VBC_MM_SLOTS=0 or VBC_MM_SLOTS_COL=0 */
 } vbc_info;
 

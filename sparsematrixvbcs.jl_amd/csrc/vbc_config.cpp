@@ -54,6 +54,8 @@ LayoutConfig make_config(int dtype, unsigned flags, unsigned narrow, const Devic
     if (!c.mm_slots) c.mm_slots_col = false;
     if (const char *e = layout_knob("VBC_MM_PLANAR_COL")) c.mm_planar_col = atoi(e) != 0;
     if (!c.mm_slots_col) c.mm_planar_col = false;
+    if (const char *e = layout_knob("VBC_MM_FWD_COL")) c.mm_fwd_col = atoi(e) != 0;
+    if (!c.mm_slots_col) c.mm_fwd_col = false;
     if (const char *e = layout_knob("VBC_SWEEP")) c.sweep_mode = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;
     c.sweep_tile = (c.esz == 8 ? 4 : 2) * kSweepTileBytes;  // measured on NS: fp64 32 KB 473 us (16 KB 508), fp32 16 KB 313 us (32 KB 353)
     // packed swept keys: NS fp64 464.5 -> 456.2 us, mixed widths 553 -> 539 us; fp32 311 -> 316 us, so

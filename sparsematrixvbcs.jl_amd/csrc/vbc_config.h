@@ -66,6 +66,11 @@ struct LayoutConfig {
                                       // at every nrhs measured: tests/test_gpu_planar.py asserts the
                                       // exact planar_mask of planar handles created under the default knobs.
                                       // VBC_MM_SLOTS=0 and VBC_MM_SLOTS_COL=0 turn it off too
+    bool mm_fwd_col = false;          // VBC_MM_FWD_COL=1: column-major B X of a forward layout of row runs or lane pairs
+                                      // runs fused (spmm_planar_fwd_col / spmm_pair_col<DOT>; planar_mask bit 25).
+                                      // Opt-in whatever the measurement says, for the reason above:
+                                      // older tests assert the exact planar_mask of handles created under the default
+                                      // knobs.  VBC_MM_SLOTS=0 and VBC_MM_SLOTS_COL=0 turn it off too
     int slot_keys16 = 1;              // VBC_SLOT_KEYS16: 0 keep 32-bit keys, 1 auto, 2 compress whenever possible
     int fork = 1;                     // VBC_FORK=0: B'x launch groups queue on the caller's stream (Launch::fork_*)
     int slot_stage = -1;              // VBC_SLOT_STAGE = 0 / 4 / 8: chunks staged in LDS per y write (-1 auto)

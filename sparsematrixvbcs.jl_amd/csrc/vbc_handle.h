@@ -175,6 +175,22 @@ constexpr int64_t kMmPlanarColMinRhs = 2;
 constexpr int64_t kMmPlanarColChunk = 4;
 int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
                            double alpha, double beta, hipStream_t s);
+// Column-major B X (forward) with nrhs >= kMmFwdColMinRhs columns runs fused over a forward layout of row runs or lane
+// pairs (mulmat_fwd_colmajor; spmm_planar_fwd_col / spmm_pair_col<DOT>): a float handle whose forward product is one
+// launch on B's own layout (no forward on C = Bᵀ, one width bucket), with no merge, slotted or swept bucket and no fused
+// small-matrix split, every planar bucket with one wave per range and chunk rows (no lane streams), of kind 1 with
+// w in {2, 3, 4} and runs of 2 or 3, or the fp64 forward lane pairs; VBC_MM_FWD_COL=1 (opt-in) and neither VBC_MM_SLOTS
+// nor VBC_MM_SLOTS_COL 0.  The one predicate of the dispatch and of planar_mask bit 25.
+bool mulmat_fuses_fwd_col(const vbc_handle *h);
+// smallest nrhs the forward column-major form runs fused at: it beats nrhs x vbc_mul by more than the spread from
+// nrhs = 2 on in every form of both workloads -- FE-2D in fp64, fp32 and narrow, the ldoor stand-in in fp64 and narrow
+// (profiles/mm_fwd_col_time.json)
+constexpr int64_t kMmFwdColMinRhs = 2;
+// columns per launch, 2 or 4: 8 columns as two NR = 4 launches sum to less over the five forms than as four NR = 2
+// launches (the same record, `fused` against `fused_by2`: nrhs8_sum_over_forms_us; FE-2D narrow alone is 2 % faster by 2)
+constexpr int64_t kMmFwdColChunk = 4;
+int mulmat_fwd_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
+                        double beta, hipStream_t s);
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
 // A cached buffer of the handle (`what`) has to grow for a product on `s`.  hipFree / hipMalloc are not stream

@@ -417,6 +417,66 @@ int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int
     return VBC_OK;
 }
 
+int launch_planar_fwd_mmc_f64(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                              double beta, bool rd, hipStream_t stream);
+int launch_planar_fwd_mmc_f32(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                              double beta, bool rd, hipStream_t stream);
+int launch_planar_fwd_mmc_f64n(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                               double beta, bool rd, hipStream_t stream);
+
+bool mulmat_fuses_fwd_col(const vbc_handle *h)
+{
+    if (!is_float(h->dtype) || !h->has_f || h->has_ft || h->f_scale || h->m <= 0) return false;
+    if (!h->cfg.mm_slots || !h->cfg.mm_slots_col || !h->cfg.mm_fwd_col) return false;
+    if (h->lf.size() != 1) return false;
+    const Launch &L = h->lf[0];
+    if (!L.bins.empty() || L.total_ranges != 0 || !L.sbins.empty() || !L.wbins.empty() || L.fuse_split) return false;
+    if (L.pbins.empty()) return false;
+    for (const SlotBin &b : L.pbins) {
+        // the forms spmm_planar_fwd_col / spmm_pair_col<DOT> cover: one wave per range, chunk rows (no lane streams),
+        // forward row runs of w in {2, 3, 4} and R in {2, 3} or the fp64 forward lane pairs; values of the compute
+        // eltype or Float32 on an fp64 handle
+        if (!b.planar || b.split > 1 || b.lanes || b.fused || VBC_ABL(b.diag != 0)) return false;
+        const bool runs = b.kind == 1 && !b.pair && b.wkey >= 2 && b.wkey <= 4 && (b.run == 2 || b.run == 3);
+        const bool pairs = b.pair && b.dot && h->esz == 8 && b.wkey == 3 && b.run == 3;
+        if (!runs && !pairs) return false;
+        if (b.vsz != 0 && !(b.vsz == 4 && h->esz == 8)) return false;
+    }
+    return true;
+}
+
+// Column-major B X of a forward layout of row runs or lane pairs (spmm_planar_fwd_col / spmm_pair_col<DOT>,
+// vbc_planar_fwd_mmc.h): per chunk of <= kMmFwdColChunk columns one launch per planar bin, then the fill list, one
+// after another on the caller's stream.  Nothing allocated, no side stream, no handle buffer: capture-safe on first
+// use, never ordered.
+int mulmat_fwd_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
+                        double beta, hipStream_t s)
+{
+    const Launch &L = h->lf[0];
+    const bool rd = beta != 0.0;
+    const auto sfn = h->esz == 4 ? launch_slots_mmc_f32 : launch_slots_mmc_f64;  // (the fill list alone: any unit of T)
+    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmFwdColChunk) {
+        const int nr = (int)std::min<int64_t>(kMmFwdColChunk, nrhs - c0);
+        const char *xs = X + c0 * ldx * h->esz;
+        char *ys = Y + c0 * ldy * h->esz;
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < L.pbins.size() && e == hipSuccess; i++) {
+            const SlotBin &pb = L.pbins[i];
+            const auto pfn = h->esz == 4 ? launch_planar_fwd_mmc_f32
+                             : pb.vsz == 4 ? launch_planar_fwd_mmc_f64n : launch_planar_fwd_mmc_f64;
+            e = (hipError_t)pfn(pb, xs, ldx, ys, ldy, nr, alpha, beta, rd, s);
+        }
+        if (e == hipSuccess && L.nfill > 0)
+            e = (hipError_t)sfn(nullptr, 0, 0, h->cfg.xcd, false, -1, L.d_fill, L.nfill, xs, ldx, ys, ldy, nr, alpha, beta,
+                                rd, s);
+        if (e != hipSuccess) {
+            set_error("spmm_planar_fwd_col launch failed: %s", hipGetErrorString(e));
+            return VBC_HIP_ERROR;
+        }
+    }
+    return VBC_OK;
+}
+
 // Multi-RHS transposed product on the tiled stream (row-major X / Y), in chunks of <= 64 columns.
 template <typename T>
 static int mulmat_t_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,

@@ -182,9 +182,12 @@ __global__ __launch_bounds__(kBlockThreads) void spmm_planar_col(const SlotBin b
                                                                                 beta, rd_i != 0, lds_out);
 }
 
-// The lane-pair form (SlotBin::pair: fp64, 3-wide stripes, runs of 3), B'x only.  Per column one d2 gather at
+// The lane-pair form (SlotBin::pair: fp64, 3-wide stripes, runs of 3).  Per column one d2 gather at
 // x_j + gi + odd, its own DPP swap and its own acc0[j] / acc1[j]; the fmadd chains are run_pair's.
-template <int NRS, bool KC, bool MASK, typename S, int NR>
+// DOT (SlotBin::dot, the forward product of 3 x 3 node blocks; vbc_planar_fwd_mmc.h's units launch it): run_pair's
+// DOT expressions per column -- the block's dot products d0 / d1 first, then acc = (live && !pad) ? acc + d : acc --
+// with the same loads, keys, gathers, swap and flush.
+template <int NRS, bool KC, bool MASK, typename S, int NR, bool DOT = false>
 __device__ __forceinline__ void run_pair_mmc(const SlotBin &b, int r, int lane, const double *__restrict__ x,
                                              int64_t ldx, double *__restrict__ y, int64_t ldy, int nr, double alpha,
                                              double beta, bool rd, int *lds_out)
@@ -299,11 +302,19 @@ __device__ __forceinline__ void run_pair_mmc(const SlotBin &b, int r, int lane, 
                 const double other = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
                 double x0 = odd ? other : xv[j][q].x, x1 = odd ? xv[j][q].x : xv[j][q].y, x2 = odd ? xv[j][q].y : other;
                 if (pad) x0 = x1 = x2 = 0.0;
-                const double n0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, fmadd((double)v[j][0].x, x0, acc0[q])))
-                                      : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, fmadd((double)v[j][0].x, x0, acc0[q])));
-                const double n1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, fmadd((double)v[j][0].y, x0, acc1[q])));
-                acc0[q] = live ? n0 : acc0[q];
-                acc1[q] = live ? n1 : acc1[q];
+                if constexpr (DOT) {
+                    const double d0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, (double)v[j][0].x * x0))
+                                          : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, (double)v[j][0].x * x0));
+                    const double d1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, (double)v[j][0].y * x0));
+                    acc0[q] = (live && !pad) ? acc0[q] + d0 : acc0[q];
+                    acc1[q] = (live && !pad) ? acc1[q] + d1 : acc1[q];
+                } else {
+                    const double n0 = odd ? fmadd((double)v[j][1].x, x2, fmadd((double)v[j][0].y, x1, fmadd((double)v[j][0].x, x0, acc0[q])))
+                                          : fmadd((double)r2.x, x2, fmadd((double)v[j][1].x, x1, fmadd((double)v[j][0].x, x0, acc0[q])));
+                    const double n1 = fmadd((double)r2.y, x2, fmadd((double)v[j][1].y, x1, fmadd((double)v[j][0].y, x0, acc1[q])));
+                    acc0[q] = live ? n0 : acc0[q];
+                    acc1[q] = live ? n1 : acc1[q];
+                }
             }
             const uint32_t lastw = KC ? bs[j] : (uint32_t)__builtin_amdgcn_readfirstlane((int)kk[j]);
             if (R + j < R1 && (lastw & kLast)) flush();
@@ -328,7 +339,7 @@ __device__ __forceinline__ void run_pair_mmc(const SlotBin &b, int r, int lane, 
 // Run-rows per pipeline stage: spmv_planar_pair's (VBC_PAIR_NRS = 4) scaled down by NR, at least one.
 __host__ __device__ constexpr int pair_mmc_step(int NR) { return VBC_PAIR_NRS / NR < 1 ? 1 : VBC_PAIR_NRS / NR; }
 
-template <bool KC, bool MASK, typename S, int NR>
+template <bool KC, bool MASK, typename S, int NR, bool DOT = false>
 __global__ __launch_bounds__(kBlockThreads) void spmm_pair_col(const SlotBin b, const double *__restrict__ x,
                                                                int64_t ldx, double *__restrict__ y, int64_t ldy, int nr,
                                                                double alpha, double beta, int rd_i)
@@ -339,7 +350,8 @@ __global__ __launch_bounds__(kBlockThreads) void spmm_pair_col(const SlotBin b, 
     const int lane = threadIdx.x & 63;
     __shared__ int outs[kWavesPerBlock * kSlotOutEntries];
     int *lds_out = outs + (threadIdx.x >> 6) * kSlotOutEntries;
-    run_pair_mmc<pair_mmc_step(NR), KC, MASK, S, NR>(b, rg, lane, x, ldx, y, ldy, nr, alpha, beta, rd_i != 0, lds_out);
+    run_pair_mmc<pair_mmc_step(NR), KC, MASK, S, NR, DOT>(b, rg, lane, x, ldx, y, ldy, nr, alpha, beta, rd_i != 0,
+                                                          lds_out);
 }
 
 }  // namespace vbc

@@ -135,7 +135,9 @@ def mulmat_(Y, A, X, alpha=1.0, beta=0.0, *, stream=None, quirks=False, engine="
     info()["planar_mask"] bit 22), column-major B'X does when it has slotted buckets of those forms only (no
     merge bucket; the same guarantee, bit 23) or plain planar / lane-pair buckets of widths 3..8 beside them (no split
     bucket, no lane streams, no swept or merge bucket; handles created under VBC_MM_PLANAR_COL=1; the same guarantee,
-    bit 24), one SpMV per column otherwise (row-major on planar buckets, lane streams, swept buckets, B·X)."""
+    bit 24), column-major B·X does on a forward layout of row runs or forward lane pairs (handles created under
+    VBC_MM_FWD_COL=1; the same guarantee, bit 25), one SpMV per column otherwise (row-major on planar buckets, lane
+    streams, swept buckets, every other B·X)."""
     B, trans = _unwrap(A)
     mem, dev, stream = _mem_device_stream(X, Y, stream)
     cdt = _compute_for(Y, B)
