@@ -455,11 +455,12 @@ int vbc_get_info(const vbc_handle *h, vbc_info *info)
     bool mm_slotted = false;
     if (mulmat_fuses(h, &mm_slotted) && mm_slotted)
         info->planar_mask |= 1 << 22;  // row-major B'X runs fused over the slotted buckets (spmm_slots)
-    if (mulmat_fuses_col(h))
+    const ColForm ct = mulmat_col_form(h, 1), cf = mulmat_col_form(h, 0);
+    if (ct == kColSlots)
         info->planar_mask |= 1 << 23;  // column-major B'X runs fused over the slotted buckets (spmm_slots_col)
-    if (mulmat_fuses_planar_col(h))
+    if (ct == kColPlanar)
         info->planar_mask |= 1 << 24;  // column-major B'X runs fused over the planar buckets (spmm_planar_col / spmm_pair_col)
-    if (mulmat_fuses_fwd_col(h))
+    if (cf == kColFwd)
         info->planar_mask |= 1 << 25;  // column-major B X runs fused over forward row runs (spmm_planar_fwd_col) or
                                        // forward lane pairs (spmm_pair_col with DOT)
     info->bytes_m = h->has_m ? h->bytes_m : h->bytes_mf;  // a forward-only multi handle: its Bᵀ panel layout
@@ -600,12 +601,9 @@ static MatPath mat_path(const vbc_handle *h, int trans, int64_t nrhs, bool rowma
     bool fused = rowmajor && trans && nrhs > 0 && mulmat_fuses(h, &slotted);
     if (slotted && nrhs < kMmSlotsMinRhs) fused = false;
     if (fused) return kMatFused;
-    // column-major: the slotted layout alone, from kMmSlotsColMinRhs columns on (spmm_slots_col)
-    if (!rowmajor && trans && nrhs >= kMmSlotsColMinRhs && mulmat_fuses_col(h)) return kMatFusedCol;
-    // ... or a layout with planar buckets, from kMmPlanarColMinRhs columns on (spmm_planar_col / spmm_pair_col)
-    if (!rowmajor && trans && nrhs >= kMmPlanarColMinRhs && mulmat_fuses_planar_col(h)) return kMatFusedCol;
-    // forward, column-major: row runs and lane pairs, from kMmFwdColMinRhs columns on (spmm_planar_fwd_col)
-    if (!rowmajor && !trans && nrhs >= kMmFwdColMinRhs && mulmat_fuses_fwd_col(h)) return kMatFusedCol;
+    // column-major: a launch with one of mulmat_col_form's forms, from the form's smallest nrhs on
+    const ColForm cf = rowmajor ? kColNone : mulmat_col_form(h, trans);
+    if (cf != kColNone && nrhs >= kColForms[cf].min_rhs) return kMatFusedCol;
     return rowmajor ? kMatColumnTemps : kMatColumns;
 }
 
@@ -622,12 +620,7 @@ static int mul_mat_device(vbc_handle *h, int trans, int64_t nrhs, const char *dX
         return mulmat_panel_any(h, trans, nrhs, dX, sxr, sxc, dY, syr, syc, alpha, beta, s);
     }
     if (path == kMatFused) return mulmat_rowmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
-    if (path == kMatFusedCol) {
-        if (!trans) return mulmat_fwd_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
-        // (a layout with planar buckets never passes mulmat_fuses_col)
-        return h->lt.pbins.empty() ? mulmat_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s)
-                                   : mulmat_planar_colmajor(h, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
-    }
+    if (path == kMatFusedCol) return mulmat_colmajor(h, trans, nrhs, dX, ldx, dY, ldy, alpha, beta, s);
     if (path == kMatColumns) {
         for (int64_t r = 0; r < nrhs && st == VBC_OK; r++)
             st = mul_dispatch(h, trans, dX + r * ldx * esz, dY + r * ldy * esz, alpha, beta, s);

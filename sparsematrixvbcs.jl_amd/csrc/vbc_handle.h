@@ -150,38 +150,30 @@ int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double 
 // dispatch (vbc_mul_mat) and of vbc_info.planar_mask bit 22 (*slotted: the layout has a slotted bucket).
 bool mulmat_fuses(const vbc_handle *h, bool *slotted);
 constexpr int64_t kMmSlotsMinRhs = 2;  // smallest nrhs the slotted part runs fused at (profiles/mm_slots_time.json)
-// Column-major B'X with nrhs >= kMmSlotsColMinRhs columns runs fused over the slotted buckets (mulmat_colmajor,
-// spmm_slots_col): mulmat_fuses's conditions for a slotted layout, no merge bucket in the launch (spmm_ranges is
-// row-major only) and VBC_MM_SLOTS_COL not 0.  The one predicate of the dispatch and of planar_mask bit 23.
-bool mulmat_fuses_col(const vbc_handle *h);
+// Column-major operands run fused when the launch of the product -- the B'x launch, or the one launch of a forward
+// product on B's own layout (no forward on C = B', one width bucket) -- has one of three forms (mulmat_col_form), on a
+// float handle with no merge bucket (spmm_ranges is row-major only), no swept bucket and no fused small-matrix split:
+//   kColSlots  B'X, slotted buckets alone, of mulmat_fuses's forms (spmm_slots_col), unless VBC_MM_SLOTS_COL=0;
+//   kColPlanar B'X, planar buckets of kind 0 with one wave per range and chunk rows (no lane streams), widths 3..8,
+//              plain or lane pairs (spmm_planar_col / spmm_pair_col), slotted buckets of kColSlots's forms beside them
+//              or none; VBC_MM_PLANAR_COL=1 (opt-in);
+//   kColFwd    B X, planar buckets alone, with one wave per range and chunk rows, of kind 1 with w in {2, 3, 4} and
+//              runs of 2 or 3 (spmm_planar_fwd_col) or the fp64 forward lane pairs (spmm_pair_col<DOT>);
+//              VBC_MM_FWD_COL=1 (opt-in).
+// VBC_MM_SLOTS=0 turns all three off, VBC_MM_SLOTS_COL=0 too (vbc_config.cpp).  The one classification of the dispatch
+// (from the form's smallest nrhs on) and of vbc_info.planar_mask bits 23 / 24 (trans) / 25 (forward).
+enum ColForm { kColNone, kColSlots, kColPlanar, kColFwd };
+ColForm mulmat_col_form(const vbc_handle *h, int trans);
 constexpr int64_t kMmSlotsColMinRhs = 2;  // smallest nrhs the column-major form runs fused at (profiles/mm_slots_col_time.json)
 // columns per launch, 4 or 8: 8 columns as two NR = 4 launches sum to 1805.9 us over the three forms on FE-2D, as one
 // NR = 8 launch to 1833.6 us (profiles/mm_slots_col_time_cap8.json, measured on a build with 8 here)
 constexpr int64_t kMmSlotsColChunk = 4;
-int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
-                    double beta, hipStream_t s);
-// Column-major B'X with nrhs >= kMmPlanarColMinRhs columns runs fused over a layout with planar buckets
-// (mulmat_planar_colmajor; spmm_planar_col / spmm_pair_col, and spmm_slots_col for the slotted buckets beside them):
-// a float handle, no swept or merge bucket, no fused small-matrix split, every planar bucket of kind 0 with one wave
-// per range, chunk rows (no lane streams), width 3..8, plain or lane pairs, the slotted buckets of spmm_slots_col's
-// forms, VBC_MM_PLANAR_COL=1 (opt-in) and neither VBC_MM_SLOTS nor VBC_MM_SLOTS_COL 0.  The one predicate of the dispatch and of
-// planar_mask bit 24.
-bool mulmat_fuses_planar_col(const vbc_handle *h);
 // smallest nrhs the planar column-major form runs fused at: it beats nrhs x vbc_mul by more than the spread from
 // nrhs = 2 on in fp64, fp32 and narrow on the ldoor stand-in (profiles/mm_planar_col_time.json)
 constexpr int64_t kMmPlanarColMinRhs = 2;
 // columns per launch, 2 or 4: 8 columns as two NR = 4 launches sum to 723.5 us over the three forms, as four NR = 2
 // launches to 833.5 us (the same record, `fused` against `fused_by2`)
 constexpr int64_t kMmPlanarColChunk = 4;
-int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
-                           double alpha, double beta, hipStream_t s);
-// Column-major B X (forward) with nrhs >= kMmFwdColMinRhs columns runs fused over a forward layout of row runs or lane
-// pairs (mulmat_fwd_colmajor; spmm_planar_fwd_col / spmm_pair_col<DOT>): a float handle whose forward product is one
-// launch on B's own layout (no forward on C = Bᵀ, one width bucket), with no merge, slotted or swept bucket and no fused
-// small-matrix split, every planar bucket with one wave per range and chunk rows (no lane streams), of kind 1 with
-// w in {2, 3, 4} and runs of 2 or 3, or the fp64 forward lane pairs; VBC_MM_FWD_COL=1 (opt-in) and neither VBC_MM_SLOTS
-// nor VBC_MM_SLOTS_COL 0.  The one predicate of the dispatch and of planar_mask bit 25.
-bool mulmat_fuses_fwd_col(const vbc_handle *h);
 // smallest nrhs the forward column-major form runs fused at: it beats nrhs x vbc_mul by more than the spread from
 // nrhs = 2 on in every form of both workloads -- FE-2D in fp64, fp32 and narrow, the ldoor stand-in in fp64 and narrow
 // (profiles/mm_fwd_col_time.json)
@@ -189,8 +181,18 @@ constexpr int64_t kMmFwdColMinRhs = 2;
 // columns per launch, 2 or 4: 8 columns as two NR = 4 launches sum to less over the five forms than as four NR = 2
 // launches (the same record, `fused` against `fused_by2`: nrhs8_sum_over_forms_us; FE-2D narrow alone is 2 % faster by 2)
 constexpr int64_t kMmFwdColChunk = 4;
-int mulmat_fwd_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
-                        double beta, hipStream_t s);
+// The table of the forms, indexed by ColForm: smallest fused nrhs, columns per launch, the kernels (for messages).
+struct ColFormRow {
+    int64_t min_rhs, chunk;
+    const char *kernel;
+};
+constexpr ColFormRow kColForms[] = {{0, 0, ""},
+                                    {kMmSlotsColMinRhs, kMmSlotsColChunk, "spmm_slots_col"},
+                                    {kMmPlanarColMinRhs, kMmPlanarColChunk, "spmm_planar_col"},
+                                    {kMmFwdColMinRhs, kMmFwdColChunk, "spmm_planar_fwd_col"}};
+// The fused column-major product of a handle with a form (trans: B'X, else B X), on the caller's stream alone.
+int mulmat_colmajor(const vbc_handle *h, int trans, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
+                    double alpha, double beta, hipStream_t s);
 int mulmat_rowmajor(vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
                     double beta, hipStream_t s);
 // A cached buffer of the handle (`what`) has to grow for a product on `s`.  hipFree / hipMalloc are not stream

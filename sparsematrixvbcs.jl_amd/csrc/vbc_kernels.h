@@ -240,6 +240,23 @@ int launch_split_multi(int esz, const SplitMulti &M, int P, const void *x, void 
                        hipStream_t s);
 int occupancy_lanes(int esz);
 
+// The fused multi-RHS launchers: one unit per family and value type (vbc_slots_mm_*.hip, vbc_slots_mmc_*.hip,
+// vbc_planar_mmc_*.hip, vbc_planar_fwd_mmc_*.hip; f64n: fp64 compute on Float32 stored values).  Each returns the
+// hipError_t of its launch; vbc_launch.hip picks the unit by (esz, vsz) (mm_unit).
+//   slots:  the slotted bins of a launch, nr <= 8 live columns at x / y; row-major operands (spmm_slots) or
+//           column-major ones (spmm_slots_col).  wonly: 2 or kWonlyNarrow2 when every bin has that form, else -1.
+//   planar: one planar bin, nr <= 4 live columns of column-major operands; B'X (spmm_planar_col / spmm_pair_col) or
+//           forward (spmm_planar_fwd_col / spmm_pair_col<DOT>).
+typedef int SlotsMmLaunch(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
+                          int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd,
+                          hipStream_t stream);
+typedef int PlanarMmLaunch(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                           double beta, bool rd, hipStream_t stream);
+SlotsMmLaunch launch_slots_mm_f64, launch_slots_mm_f32, launch_slots_mm_f64n;
+SlotsMmLaunch launch_slots_mmc_f64, launch_slots_mmc_f32, launch_slots_mmc_f64n;
+PlanarMmLaunch launch_planar_mmc_f64, launch_planar_mmc_f32, launch_planar_mmc_f64n;
+PlanarMmLaunch launch_planar_fwd_mmc_f64, launch_planar_fwd_mmc_f32, launch_planar_fwd_mmc_f64n;
+
 __host__ __device__ constexpr int vec_elems(int esz, int w)
 {
     return esz == 8 ? (w % 2 == 0 ? 2 : 1) : (w % 4 == 0 ? 4 : (w % 2 == 0 ? 2 : 1));
@@ -1005,6 +1022,18 @@ __global__ __launch_bounds__(kBlockThreads) void fixup(const Bin *__restrict__ b
         T *yo = y + fill[i - total_ranges];
         *yo = rd_i ? beta * *yo : T(0);
     }
+}
+
+// The fill list of a column-major multi-RHS launch (stripes that own no stored row): y = beta * y, or 0, in each of
+// the nr columns (blockIdx.y), with fixup's expression.
+template <typename T>
+__global__ __launch_bounds__(kBlockThreads) void fill_cols(const int32_t *__restrict__ fill, int nfill,
+                                                           T *__restrict__ y, int64_t ldy, T beta, int rd_i)
+{
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (i >= nfill) return;
+    T *yo = y + (int64_t)blockIdx.y * ldy + fill[i];
+    *yo = rd_i ? beta * *yo : T(0);
 }
 
 // y = beta * y (forward products with several width buckets accumulate bucket by bucket).

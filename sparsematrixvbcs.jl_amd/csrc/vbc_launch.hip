@@ -1,5 +1,8 @@
 // libvbc kernel launches of the vector products: merge kernel (vbc_kernels.h) + slotted kernel
-// (vbc_slots.hip), their fix-up passes, and the fused vector multi-RHS kernels (spmm_ranges, spmm_slots).
+// (vbc_slots.hip) and their fix-up passes, and the fused vector multi-RHS products -- row-major B'X over the merge
+// and slotted layouts (mulmat_rowmajor: spmm_ranges, spmm_slots), and column-major B'X and B X through one driver
+// (mulmat_colmajor) over the forms of mulmat_col_form: spmm_slots_col, spmm_planar_col / spmm_pair_col,
+// spmm_planar_fwd_col / spmm_pair_col<DOT>, and fill_cols for the fill list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -248,12 +251,18 @@ int mul_dispatch(const vbc_handle *h, int trans, const void *x, void *y, double 
                                : mul_device<float>(h, trans, x, y, alpha, beta, stream);
 }
 
-int launch_slots_mm_f64(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
-                        int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
-int launch_slots_mm_f32(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
-                        int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
-int launch_slots_mm_f64n(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
-                         int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream);
+// The units of a fused multi-RHS launcher family (vbc_kernels.h): fp64, fp32, fp64 on Float32 stored values.
+static SlotsMmLaunch *const kSlotsMm[3] = {launch_slots_mm_f64, launch_slots_mm_f32, launch_slots_mm_f64n};
+static SlotsMmLaunch *const kSlotsMmc[3] = {launch_slots_mmc_f64, launch_slots_mmc_f32, launch_slots_mmc_f64n};
+static PlanarMmLaunch *const kPlanarMmc[3] = {launch_planar_mmc_f64, launch_planar_mmc_f32, launch_planar_mmc_f64n};
+static PlanarMmLaunch *const kPlanarFwdMmc[3] = {launch_planar_fwd_mmc_f64, launch_planar_fwd_mmc_f32,
+                                                 launch_planar_fwd_mmc_f64n};
+// ... and the one of a handle of esz bytes for bins whose stored values take vsz bytes (SlotBin::vsz: 0 = esz).
+template <typename F>
+static F *mm_unit(F *const (&units)[3], int esz, int vsz)
+{
+    return esz == 4 ? units[1] : vsz == 4 ? units[2] : units[0];
+}
 
 // The slotted bins of the B'x launch (at least one) all have a form spmm_slots / spmm_slots_col covers: kind 0, a
 // compile-time width, one segment per lane slot or the fp32 w = 2 two-segment rows; keys and stored value type
@@ -269,6 +278,16 @@ static bool slots_mm_forms(const vbc_handle *h)
         if (b.vsz != f.vsz || (b.kc != 0) != (f.kc != 0) || VBC_ABL(b.diag != 0)) return false;
     }
     return true;
+}
+
+// The one-width kernel of a multi-RHS slotted launch: 2 / kWonlyNarrow2 when every slotted bin has w = 2 in the plain /
+// the narrow-row form, else -1.
+static int slots_mm_wonly(const Launch &L)
+{
+    int wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
+    for (const SlotBin &b : L.sbins)
+        if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
+    return wonly;
 }
 
 bool mulmat_fuses(const vbc_handle *h, bool *slotted)
@@ -289,15 +308,12 @@ static int mulmat_slots(const vbc_handle *h, int64_t nrhs, const char *X, int64_
                         double alpha, double beta, hipStream_t s)
 {
     const Launch &L = h->lt;
-    int wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
-    for (const SlotBin &b : L.sbins)
-        if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
-    const int vsz = L.sbins[0].vsz > 0 ? L.sbins[0].vsz : h->esz;
+    const int wonly = slots_mm_wonly(L);
+    SlotsMmLaunch *const fn = mm_unit(kSlotsMm, h->esz, L.sbins[0].vsz);
     for (int64_t c0 = 0; c0 < nrhs; c0 += 8) {
         const int nr = (int)std::min<int64_t>(8, nrhs - c0);
         const char *xs = X + c0 * h->esz;
         char *ys = Y + c0 * h->esz;
-        const auto fn = h->esz == 4 ? launch_slots_mm_f32 : vsz == 4 ? launch_slots_mm_f64n : launch_slots_mm_f64;
         const hipError_t e = (hipError_t)fn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, L.sbins[0].kc != 0,
                                             wonly, xs, ldx, ys, ldy, nr, alpha, beta, beta != 0.0, s);
         if (e != hipSuccess) {
@@ -308,169 +324,81 @@ static int mulmat_slots(const vbc_handle *h, int64_t nrhs, const char *X, int64_
     return VBC_OK;
 }
 
-int launch_slots_mmc_f64(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
-                         const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
-                         double alpha, double beta, bool rd, hipStream_t stream);
-int launch_slots_mmc_f32(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
-                         const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
-                         double alpha, double beta, bool rd, hipStream_t stream);
-int launch_slots_mmc_f64n(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly,
-                          const int32_t *d_fill, int nfill, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
-                          double alpha, double beta, bool rd, hipStream_t stream);
-
-bool mulmat_fuses_col(const vbc_handle *h)
+// One planar bin has a form the column-major kernels cover: one wave per range and chunk rows (not split, no lane
+// streams), values of the compute eltype or Float32 on an fp64 handle, and
+//   B'X:     kind 0, widths 3..8 in runs of 1..3 (spmm_planar_col) or the fp64 lane pairs (spmm_pair_col);
+//   forward: kind 1 row runs of w in {2, 3, 4} and R in {2, 3} (spmm_planar_fwd_col) or the fp64 forward lane pairs
+//            (spmm_pair_col<DOT>).
+static bool planar_col_form(const vbc_handle *h, const SlotBin &b, bool fwd)
 {
-    bool slotted = false;
-    if (!h->cfg.mm_slots_col || !mulmat_fuses(h, &slotted) || !slotted) return false;
-    return h->lt.bins.empty() && h->lt.total_ranges == 0;  // merge buckets: per column
+    if (!b.planar || b.split > 1 || b.lanes || b.fused || VBC_ABL(b.diag != 0)) return false;
+    if (b.vsz != 0 && !(b.vsz == 4 && h->esz == 8)) return false;
+    const bool pairs = b.pair && h->esz == 8 && b.wkey == 3 && b.run == 3;
+    if (fwd) return b.pair ? pairs && b.dot : b.kind == 1 && b.wkey >= 2 && b.wkey <= 4 && (b.run == 2 || b.run == 3);
+    if (b.kind != 0 || b.dot || b.holes || b.ks > 1) return false;
+    return b.pair ? pairs : b.wkey >= 3 && b.wkey <= 8 && b.run >= 1 && b.run <= 3;
 }
 
-// Column-major B'X of a slotted layout without merge buckets (spmm_slots_col, vbc_slots_mmc.h): chunks of
-// <= kMmSlotsColChunk columns one after another on the caller's stream, each followed by the fill list of its
-// columns.  Nothing allocated, no side stream, no handle buffer: capture-safe on first use, never ordered.
-int mulmat_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
-                    double beta, hipStream_t s)
+// The knobs need no test against each other here: LayoutConfig (vbc_config.cpp) turns mm_slots_col off with mm_slots,
+// and mm_planar_col and mm_fwd_col off with mm_slots_col.
+ColForm mulmat_col_form(const vbc_handle *h, int trans)
 {
-    const Launch &L = h->lt;
-    int wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
-    for (const SlotBin &b : L.sbins)
-        if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
-    const int vsz = L.sbins[0].vsz > 0 ? L.sbins[0].vsz : h->esz;
-    const auto fn = h->esz == 4 ? launch_slots_mmc_f32 : vsz == 4 ? launch_slots_mmc_f64n : launch_slots_mmc_f64;
-    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmSlotsColChunk) {
-        const int nr = (int)std::min<int64_t>(kMmSlotsColChunk, nrhs - c0);
-        const hipError_t e = (hipError_t)fn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, L.sbins[0].kc != 0,
-                                            wonly, L.d_fill, L.nfill, X + c0 * ldx * h->esz, ldx, Y + c0 * ldy * h->esz,
-                                            ldy, nr, alpha, beta, beta != 0.0, s);
-        if (e != hipSuccess) {
-            set_error("spmm_slots_col launch failed: %s", hipGetErrorString(e));
-            return VBC_HIP_ERROR;
-        }
-    }
-    return VBC_OK;
+    if (!is_float(h->dtype)) return kColNone;
+    // forward: one launch on B's own layout (no forward on C = B', one width bucket)
+    if (trans ? !h->has_t || h->n <= 0 : !h->has_f || h->has_ft || h->f_scale || h->m <= 0 || h->lf.size() != 1)
+        return kColNone;
+    const Launch &L = trans ? h->lt : h->lf[0];
+    // merge buckets (spmm_ranges is row-major only), swept buckets, the fused small-matrix split (it needs a planar
+    // bucket) and forward slotted buckets: per column
+    if (!L.bins.empty() || L.total_ranges != 0 || !L.wbins.empty() || L.fuse_split) return kColNone;
+    if (!L.sbins.empty() && !(trans && slots_mm_forms(h))) return kColNone;
+    if (L.pbins.empty()) return trans && !L.sbins.empty() && h->cfg.mm_slots_col ? kColSlots : kColNone;
+    if (!(trans ? h->cfg.mm_planar_col : h->cfg.mm_fwd_col)) return kColNone;
+    for (const SlotBin &b : L.pbins)
+        if (!planar_col_form(h, b, !trans)) return kColNone;
+    return trans ? kColPlanar : kColFwd;
 }
 
-int launch_planar_mmc_f64(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                          double beta, bool rd, hipStream_t stream);
-int launch_planar_mmc_f32(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                          double beta, bool rd, hipStream_t stream);
-int launch_planar_mmc_f64n(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                           double beta, bool rd, hipStream_t stream);
-
-bool mulmat_fuses_planar_col(const vbc_handle *h)
+static hipError_t launch_fill_cols(int esz, const int32_t *d_fill, int nfill, void *y, int64_t ldy, int nr, double beta,
+                                   bool rd, hipStream_t s)
 {
-    const Launch &L = h->lt;
-    if (!h->has_t || h->n <= 0 || h->dtype == VBC_I64) return false;
-    if (!h->cfg.mm_slots || !h->cfg.mm_slots_col || !h->cfg.mm_planar_col) return false;
-    if (!L.wbins.empty() || !L.bins.empty() || L.total_ranges != 0 || L.fuse_split) return false;
-    if (L.pbins.empty()) return false;
-    for (const SlotBin &b : L.pbins) {
-        // the forms spmm_planar_col / spmm_pair_col cover: kind 0, one wave per range, chunk rows (no lane streams),
-        // widths 3..8, plain or the fp64 lane pairs; values of the compute eltype or Float32 on an fp64 handle
-        if (b.kind != 0 || !b.planar || b.split > 1 || b.fused || b.lanes || b.dot || b.holes || b.ks > 1) return false;
-        if (b.wkey < 3 || b.wkey > 8 || b.run < 1 || b.run > 3 || VBC_ABL(b.diag != 0)) return false;
-        if (b.pair && (h->esz != 8 || b.wkey != 3 || b.run != 3)) return false;
-        if (b.vsz != 0 && !(b.vsz == 4 && h->esz == 8)) return false;
-    }
-    return L.sbins.empty() || slots_mm_forms(h);
+    const dim3 grid((nfill + kBlockThreads - 1) / kBlockThreads, nr), blk(kBlockThreads);
+    if (esz == 8)
+        hipLaunchKernelGGL((fill_cols<double>), grid, blk, 0, s, d_fill, nfill, static_cast<double *>(y), ldy, beta, (int)rd);
+    else
+        hipLaunchKernelGGL((fill_cols<float>), grid, blk, 0, s, d_fill, nfill, static_cast<float *>(y), ldy, (float)beta,
+                           (int)rd);
+    return hipGetLastError();
 }
 
-// Column-major B'X of a layout with planar buckets (spmm_planar_col / spmm_pair_col, vbc_planar_mmc.h): per chunk of
-// <= kMmPlanarColChunk columns the slotted bins (spmm_slots_col), then one launch per planar bin, then the fill list,
-// one after another on the caller's stream.  Nothing allocated, no side stream, no handle buffer: capture-safe on
-// first use, never ordered.
-int mulmat_planar_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
-                           double alpha, double beta, hipStream_t s)
+// The fused column-major product of a handle whose launch (B'x for trans, else the forward one) has a form of
+// mulmat_col_form: per chunk of the form's columns (kColForms) the slotted bins if any (spmm_slots_col), then one
+// launch per planar bin, then the fill list of the chunk's columns if any, one after another on the caller's stream.
+// Nothing allocated, no side stream, no handle buffer: capture-safe on first use, never ordered.
+int mulmat_colmajor(const vbc_handle *h, int trans, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy,
+                    double alpha, double beta, hipStream_t s)
 {
-    const Launch &L = h->lt;
+    const ColFormRow &form = kColForms[mulmat_col_form(h, trans)];
+    if (form.chunk == 0) return fail(VBC_INVALID_ARG, "internal: the layout has no fused column-major form");
+    const Launch &L = trans ? h->lt : h->lf[0];
     const bool rd = beta != 0.0;
-    int wonly = -1;
-    auto sfn = h->esz == 4 ? launch_slots_mmc_f32 : launch_slots_mmc_f64;  // (the fill list alone: any unit of T)
-    if (!L.sbins.empty()) {
-        wonly = L.sbins[0].wkey == 2 ? (L.sbins[0].spl == 2 ? kWonlyNarrow2 : 2) : -1;
-        for (const SlotBin &b : L.sbins)
-            if (b.wkey != 2 || (b.spl == 2) != (wonly == kWonlyNarrow2)) wonly = -1;
-        if (h->esz == 8 && L.sbins[0].vsz == 4) sfn = launch_slots_mmc_f64n;
-    }
-    const bool skc = !L.sbins.empty() && L.sbins[0].kc != 0;
-    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmPlanarColChunk) {
-        const int nr = (int)std::min<int64_t>(kMmPlanarColChunk, nrhs - c0);
+    for (int64_t c0 = 0; c0 < nrhs; c0 += form.chunk) {
+        const int nr = (int)std::min<int64_t>(form.chunk, nrhs - c0);
         const char *xs = X + c0 * ldx * h->esz;
         char *ys = Y + c0 * ldy * h->esz;
         hipError_t e = hipSuccess;
         if (L.slot_ranges > 0)
-            e = (hipError_t)sfn(L.d_sbins, (int)L.sbins.size(), L.slot_ranges, h->cfg.xcd, skc, wonly, nullptr, 0, xs, ldx,
-                                ys, ldy, nr, alpha, beta, rd, s);
+            e = (hipError_t)mm_unit(kSlotsMmc, h->esz, L.sbins[0].vsz)(L.d_sbins, (int)L.sbins.size(), L.slot_ranges,
+                                                                       h->cfg.xcd, L.sbins[0].kc != 0, slots_mm_wonly(L),
+                                                                       xs, ldx, ys, ldy, nr, alpha, beta, rd, s);
         for (size_t i = 0; i < L.pbins.size() && e == hipSuccess; i++) {
             const SlotBin &pb = L.pbins[i];
-            const auto pfn = h->esz == 4 ? launch_planar_mmc_f32 : pb.vsz == 4 ? launch_planar_mmc_f64n : launch_planar_mmc_f64;
-            e = (hipError_t)pfn(pb, xs, ldx, ys, ldy, nr, alpha, beta, rd, s);
+            e = (hipError_t)mm_unit(trans ? kPlanarMmc : kPlanarFwdMmc, h->esz, pb.vsz)(pb, xs, ldx, ys, ldy, nr, alpha,
+                                                                                       beta, rd, s);
         }
-        if (e == hipSuccess && L.nfill > 0)
-            e = (hipError_t)sfn(L.d_sbins, (int)L.sbins.size(), 0, h->cfg.xcd, skc, wonly, L.d_fill, L.nfill, xs, ldx, ys,
-                                ldy, nr, alpha, beta, rd, s);
+        if (e == hipSuccess && L.nfill > 0) e = launch_fill_cols(h->esz, L.d_fill, L.nfill, ys, ldy, nr, beta, rd, s);
         if (e != hipSuccess) {
-            set_error("spmm_planar_col launch failed: %s", hipGetErrorString(e));
-            return VBC_HIP_ERROR;
-        }
-    }
-    return VBC_OK;
-}
-
-int launch_planar_fwd_mmc_f64(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                              double beta, bool rd, hipStream_t stream);
-int launch_planar_fwd_mmc_f32(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                              double beta, bool rd, hipStream_t stream);
-int launch_planar_fwd_mmc_f64n(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
-                               double beta, bool rd, hipStream_t stream);
-
-bool mulmat_fuses_fwd_col(const vbc_handle *h)
-{
-    if (!is_float(h->dtype) || !h->has_f || h->has_ft || h->f_scale || h->m <= 0) return false;
-    if (!h->cfg.mm_slots || !h->cfg.mm_slots_col || !h->cfg.mm_fwd_col) return false;
-    if (h->lf.size() != 1) return false;
-    const Launch &L = h->lf[0];
-    if (!L.bins.empty() || L.total_ranges != 0 || !L.sbins.empty() || !L.wbins.empty() || L.fuse_split) return false;
-    if (L.pbins.empty()) return false;
-    for (const SlotBin &b : L.pbins) {
-        // the forms spmm_planar_fwd_col / spmm_pair_col<DOT> cover: one wave per range, chunk rows (no lane streams),
-        // forward row runs of w in {2, 3, 4} and R in {2, 3} or the fp64 forward lane pairs; values of the compute
-        // eltype or Float32 on an fp64 handle
-        if (!b.planar || b.split > 1 || b.lanes || b.fused || VBC_ABL(b.diag != 0)) return false;
-        const bool runs = b.kind == 1 && !b.pair && b.wkey >= 2 && b.wkey <= 4 && (b.run == 2 || b.run == 3);
-        const bool pairs = b.pair && b.dot && h->esz == 8 && b.wkey == 3 && b.run == 3;
-        if (!runs && !pairs) return false;
-        if (b.vsz != 0 && !(b.vsz == 4 && h->esz == 8)) return false;
-    }
-    return true;
-}
-
-// Column-major B X of a forward layout of row runs or lane pairs (spmm_planar_fwd_col / spmm_pair_col<DOT>,
-// vbc_planar_fwd_mmc.h): per chunk of <= kMmFwdColChunk columns one launch per planar bin, then the fill list, one
-// after another on the caller's stream.  Nothing allocated, no side stream, no handle buffer: capture-safe on first
-// use, never ordered.
-int mulmat_fwd_colmajor(const vbc_handle *h, int64_t nrhs, const char *X, int64_t ldx, char *Y, int64_t ldy, double alpha,
-                        double beta, hipStream_t s)
-{
-    const Launch &L = h->lf[0];
-    const bool rd = beta != 0.0;
-    const auto sfn = h->esz == 4 ? launch_slots_mmc_f32 : launch_slots_mmc_f64;  // (the fill list alone: any unit of T)
-    for (int64_t c0 = 0; c0 < nrhs; c0 += kMmFwdColChunk) {
-        const int nr = (int)std::min<int64_t>(kMmFwdColChunk, nrhs - c0);
-        const char *xs = X + c0 * ldx * h->esz;
-        char *ys = Y + c0 * ldy * h->esz;
-        hipError_t e = hipSuccess;
-        for (size_t i = 0; i < L.pbins.size() && e == hipSuccess; i++) {
-            const SlotBin &pb = L.pbins[i];
-            const auto pfn = h->esz == 4 ? launch_planar_fwd_mmc_f32
-                             : pb.vsz == 4 ? launch_planar_fwd_mmc_f64n : launch_planar_fwd_mmc_f64;
-            e = (hipError_t)pfn(pb, xs, ldx, ys, ldy, nr, alpha, beta, rd, s);
-        }
-        if (e == hipSuccess && L.nfill > 0)
-            e = (hipError_t)sfn(nullptr, 0, 0, h->cfg.xcd, false, -1, L.d_fill, L.nfill, xs, ldx, ys, ldy, nr, alpha, beta,
-                                rd, s);
-        if (e != hipSuccess) {
-            set_error("spmm_planar_fwd_col launch failed: %s", hipGetErrorString(e));
+            set_error("%s launch failed: %s", form.kernel, hipGetErrorString(e));
             return VBC_HIP_ERROR;
         }
     }

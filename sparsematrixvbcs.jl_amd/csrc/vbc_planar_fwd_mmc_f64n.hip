@@ -3,4 +3,5 @@
 #define VBC_PLANAR_T double
 #define VBC_PLANAR_S float
 #define VBC_PLANAR_SUFFIX f64n
-#include "vbc_planar_fwd_mmc_launch.inc"
+#define VBC_PLANAR_FWD
+#include "vbc_planar_mmc_launch.inc"

@@ -5,7 +5,7 @@
 // X (m x nrhs) and Y (n x nrhs) are column-major: X[i + j * ldx], Y[i + j * ldy] with ldx >= m, ldy >= n (a Julia
 // Matrix).  run_planar_mmc is run_planar<T, W_, U, false, 0, KC, RUN, MASK, S> and run_pair_mmc is
 // run_pair<NRS, false, 0, KC, MASK, false, S> with the accumulators widened by a column index, the step
-// run_slots_mmc (vbc_slots_mmc.h) took from run_slots: the same SlotBin, ranges, chunks, RUN-aligned clamped
+// run_slots_mm (vbc_slots_mm.h, kRhsCols) took from run_slots: the same SlotBin, ranges, chunks, RUN-aligned clamped
 // unconditional loads, keys in both forms, nlive masking, `live` / `pad` selects, two-stage ping-pong and the
 // y-offset table staged through LDS (kSlotOutEntries).  Each stored value is loaded once and meets the NR
 // right-hand sides of its x row in NR fused multiply-adds, rows in stored order, and every column keeps

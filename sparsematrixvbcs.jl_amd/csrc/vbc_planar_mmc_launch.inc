@@ -1,12 +1,14 @@
-// spmm_planar_col / spmm_pair_col launchers for one value type (included by vbc_planar_mmc_f64.hip /
-// vbc_planar_mmc_f32.hip / vbc_planar_mmc_f64n.hip, which define VBC_PLANAR_T and VBC_PLANAR_SUFFIX, and
-// VBC_PLANAR_S when the stored values are narrower than VBC_PLANAR_T): one translation unit per type so they
-// compile in parallel.
+// The column-major multi-RHS launchers of one planar bin for one value type: spmm_planar_col / spmm_pair_col (B'X;
+// included by vbc_planar_mmc_f64.hip / vbc_planar_mmc_f32.hip / vbc_planar_mmc_f64n.hip) and, with VBC_PLANAR_FWD
+// defined, spmm_planar_fwd_col / spmm_pair_col<..., DOT> (forward; vbc_planar_fwd_mmc_*.hip).  The unit defines
+// VBC_PLANAR_T and VBC_PLANAR_SUFFIX, and VBC_PLANAR_S when the stored values are narrower than VBC_PLANAR_T: one
+// translation unit per family and type so they compile in parallel, each with the kernels of its own family only.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
-#include "vbc_planar_mmc.h"
+#include "vbc_planar_fwd_mmc.h"  // (includes vbc_planar_mmc.h)
 
 #ifndef VBC_PLANAR_S
 #define VBC_PLANAR_S VBC_PLANAR_T
@@ -14,86 +16,67 @@
 
 namespace vbc {
 
-template <typename T, typename S, int W_, bool KC, int RUN, int NR>
-static void launch_pmmc_nr(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha,
-                           double beta, bool rd, hipStream_t s)
-{
-    const int grid = (hb.nranges + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (hb.mask)
-        hipLaunchKernelGGL((spmm_planar_col<T, W_, KC, RUN, true, S, NR>), dim3(grid), dim3(kBlockThreads), 0, s, hb, x,
-                           ldx, y, ldy, nr, (T)alpha, (T)beta, (int)rd);
-    else
-        hipLaunchKernelGGL((spmm_planar_col<T, W_, KC, RUN, false, S, NR>), dim3(grid), dim3(kBlockThreads), 0, s, hb, x,
-                           ldx, y, ldy, nr, (T)alpha, (T)beta, (int)rd);
-}
+// A bin form at its compile-time parameters: kernel<NR, MASK> is its instance for NR columns in the natural or the
+// masked chunk order.
+template <typename T, typename S, int W_, int RUN, bool KC>
+struct RunsCol {  // B'X row chunks: w in 3..8, runs of 1..3 (spmv_planar's forms)
+    template <int NR, bool MASK>
+    static constexpr auto kernel = spmm_planar_col<T, W_, KC, RUN, MASK, S, NR>;
+};
+template <typename T, typename S, int W_, int R, bool KC>
+struct RunsFwdCol {  // forward row runs: w in {2, 3, 4}, R in {2, 3} (spmv_planar_fwd's forms)
+    template <int NR, bool MASK>
+    static constexpr auto kernel = spmm_planar_fwd_col<T, W_, R, KC, MASK, S, NR>;
+};
+template <typename S, bool KC, bool DOT>
+struct PairCol {  // lane pairs: fp64, w = 3, runs of 3; DOT: the forward ones
+    template <int NR, bool MASK>
+    static constexpr auto kernel = spmm_pair_col<KC, MASK, S, NR, DOT>;
+};
 
 // NR = 2 or 4, the smallest that holds the nr live columns (every instance is free of scratch at NR = 4: DESIGN.md
-// §11.2 has the compiler's table, so no width falls back to NR = 2 chunks)
-template <typename T, typename S, int W_, bool KC, int RUN>
-static void launch_pmmc_w(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha,
-                          double beta, bool rd, hipStream_t s)
-{
-    if (nr <= 2) launch_pmmc_nr<T, S, W_, KC, RUN, 2>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
-    else launch_pmmc_nr<T, S, W_, KC, RUN, 4>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
-}
-
-template <typename T, typename S, bool KC, int RUN>
-static int launch_pmmc_r(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha,
-                         double beta, bool rd, hipStream_t s)
-{
-    switch (hb.wkey) {
-    case 3: launch_pmmc_w<T, S, 3, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    case 4: launch_pmmc_w<T, S, 4, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    case 5: launch_pmmc_w<T, S, 5, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    case 6: launch_pmmc_w<T, S, 6, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    case 7: launch_pmmc_w<T, S, 7, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    case 8: launch_pmmc_w<T, S, 8, KC, RUN>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-    return (int)hipGetLastError();
-}
-
-template <typename T, typename S, bool KC>
-static int launch_pmmc_t(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha,
-                         double beta, bool rd, hipStream_t s)
-{
-    switch (hb.run) {
-    case 1: return launch_pmmc_r<T, S, KC, 1>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
-    case 2: return launch_pmmc_r<T, S, KC, 2>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
-    case 3: return launch_pmmc_r<T, S, KC, 3>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-template <typename S, bool KC>
-static int launch_pair_mmc(const SlotBin &hb, const double *x, int64_t ldx, double *y, int64_t ldy, int nr,
-                           double alpha, double beta, bool rd, hipStream_t s)
+// §11.2 and §11.3 have the compiler's tables, so no form falls back to NR = 2 chunks), by MASK.
+template <typename FORM, typename T>
+static int launch_form(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha, double beta,
+                       bool rd, hipStream_t s)
 {
     const dim3 grid((hb.nranges + kWavesPerBlock - 1) / kWavesPerBlock), blk(kBlockThreads);
-#define VBC_PAIR_MMC(MASK)                                                                                             \
-    do {                                                                                                               \
-        if (nr <= 2)                                                                                                   \
-            hipLaunchKernelGGL((spmm_pair_col<KC, MASK, S, 2>), grid, blk, 0, s, hb, x, ldx, y, ldy, nr, alpha, beta,  \
-                               (int)rd);                                                                               \
-        else                                                                                                           \
-            hipLaunchKernelGGL((spmm_pair_col<KC, MASK, S, 4>), grid, blk, 0, s, hb, x, ldx, y, ldy, nr, alpha, beta,  \
-                               (int)rd);                                                                               \
-    } while (0)
-    if (hb.mask) VBC_PAIR_MMC(true);
-    else VBC_PAIR_MMC(false);
-#undef VBC_PAIR_MMC
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, hb, x, ldx, y, ldy, nr, (T)alpha, (T)beta, (int)rd);
+    };
+    if (hb.mask) nr <= 2 ? go(FORM::template kernel<2, true>) : go(FORM::template kernel<4, true>);
+    else nr <= 2 ? go(FORM::template kernel<2, false>) : go(FORM::template kernel<4, false>);
     return (int)hipGetLastError();
+}
+
+template <bool FWD, typename T, typename S, bool KC>
+static int launch_runs(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha, double beta,
+                       bool rd, hipStream_t s)
+{
+#define VBC_WR(W, R)                    \
+    if (hb.wkey == W && hb.run == R)    \
+        return launch_form<std::conditional_t<FWD, RunsFwdCol<T, S, W, R, KC>, RunsCol<T, S, W, R, KC>>>( \
+            hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
+    if constexpr (FWD) {
+        VBC_WR(2, 2) VBC_WR(2, 3) VBC_WR(3, 2) VBC_WR(3, 3) VBC_WR(4, 2) VBC_WR(4, 3)
+    } else {
+#define VBC_W(W) VBC_WR(W, 1) VBC_WR(W, 2) VBC_WR(W, 3)
+        VBC_W(3) VBC_W(4) VBC_W(5) VBC_W(6) VBC_W(7) VBC_W(8)
+#undef VBC_W
+    }
+#undef VBC_WR
+    return (int)hipErrorInvalidValue;
 }
 
 // lane pairs: fp64, w = 3, runs of 3 (no fp32 form: a missing kernel is an error)
-template <typename T, typename S>
-static int launch_pair_mmc_t(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha,
-                             double beta, bool rd, hipStream_t s)
+template <bool DOT, typename T, typename S>
+static int launch_pairs(const SlotBin &hb, const T *x, int64_t ldx, T *y, int64_t ldy, int nr, double alpha, double beta,
+                        bool rd, hipStream_t s)
 {
     if constexpr (sizeof(T) == 8) {
         if (hb.wkey != 3 || hb.run != 3) return (int)hipErrorInvalidValue;
-        return hb.kc ? launch_pair_mmc<S, true>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s)
-                     : launch_pair_mmc<S, false>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
+        return hb.kc ? launch_form<PairCol<S, true, DOT>>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s)
+                     : launch_form<PairCol<S, false, DOT>>(hb, x, ldx, y, ldy, nr, alpha, beta, rd, s);
     } else {
         return (int)hipErrorInvalidValue;
     }
@@ -101,11 +84,20 @@ static int launch_pair_mmc_t(const SlotBin &hb, const T *x, int64_t ldx, T *y, i
 
 #define VBC_CAT2(a, b) a##b
 #define VBC_CAT(a, b) VBC_CAT2(a, b)
+#ifdef VBC_PLANAR_FWD
+#define VBC_PLANAR_ENTRY VBC_CAT(launch_planar_fwd_mmc_, VBC_PLANAR_SUFFIX)
+constexpr bool kFwd = true;
+#else
+#define VBC_PLANAR_ENTRY VBC_CAT(launch_planar_mmc_, VBC_PLANAR_SUFFIX)
+constexpr bool kFwd = false;
+#endif
 
-// One planar bin (plain or lane-pair, kind 0, not split, no lane streams), nr <= 4 live columns at x / y (column
-// strides ldx / ldy).  The bin's stored value type must be this unit's (the caller picks the unit by SlotBin::vsz).
-int VBC_CAT(launch_planar_mmc_, VBC_PLANAR_SUFFIX)(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy,
-                                                   int nr, double alpha, double beta, bool rd, hipStream_t stream)
+// One planar bin, one wave per range and chunk rows (not split, no lane streams), nr <= 4 live columns at x / y (column
+// strides ldx / ldy): of kind 0 in row chunks or lane pairs (B'X), or of kind 1 in row runs or the lane pairs with
+// SlotBin::dot (forward).  The bin's stored value type must be this unit's (the caller picks the unit by SlotBin::vsz).
+// A form without a kernel is an error.
+int VBC_PLANAR_ENTRY(const SlotBin &hb, const void *x, int64_t ldx, void *y, int64_t ldy, int nr, double alpha,
+                     double beta, bool rd, hipStream_t stream)
 {
     typedef VBC_PLANAR_T T;
     typedef VBC_PLANAR_S S;
@@ -113,11 +105,13 @@ int VBC_CAT(launch_planar_mmc_, VBC_PLANAR_SUFFIX)(const SlotBin &hb, const void
     T *ys = static_cast<T *>(y);
     if (nr < 1 || nr > 4) return (int)hipErrorInvalidValue;
     if (hb.nranges <= 0) return (int)hipSuccess;
-    if (hb.kind != 0 || hb.split > 1 || hb.lanes || hb.dot) return (int)hipErrorInvalidValue;
+    if (hb.split > 1 || hb.lanes) return (int)hipErrorInvalidValue;
     if ((hb.vsz == 4) != (sizeof(S) < sizeof(T)) || (hb.vsz != 0 && hb.vsz != 4)) return (int)hipErrorInvalidValue;
-    if (hb.pair) return launch_pair_mmc_t<T, S>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream);
-    return hb.kc ? launch_pmmc_t<T, S, true>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream)
-                 : launch_pmmc_t<T, S, false>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream);
+    const bool form = kFwd ? !hb.fused && (hb.pair ? hb.dot != 0 : hb.kind == 1) : hb.kind == 0 && !hb.dot;
+    if (!form) return (int)hipErrorInvalidValue;
+    if (hb.pair) return launch_pairs<kFwd, T, S>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream);
+    return hb.kc ? launch_runs<kFwd, T, S, true>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream)
+                 : launch_runs<kFwd, T, S, false>(hb, xs, ldx, ys, ldy, nr, alpha, beta, rd, stream);
 }
 
 }  // namespace vbc

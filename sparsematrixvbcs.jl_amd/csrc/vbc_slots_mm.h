@@ -1,23 +1,36 @@
-// gfx950 slotted-segment multi-RHS kernel: Y = alpha * B' X + beta * Y over the slotted B'x layout of
-// vbc_slots.h (device code, included by the vbc_slots_mm_*.hip translation units only).
+// gfx950 slotted-segment multi-RHS kernels: Y = alpha * B' X + beta * Y over the slotted B'x layout of
+// vbc_slots.h (device code, included by the vbc_slots_mm_*.hip and vbc_slots_mmc_*.hip translation units only).
 //
-// X (m x nrhs) and Y (n x nrhs) are row-major (right-hand sides interleaved: X[i * ldx + j]).  The kernel
-// reads the SlotBin arena of spmv_slots -- no layout of its own -- and keeps run_slots's lane -> (slot, sub)
-// map, chunks, ranges, PAD / LAST handling and clamped unconditional loads (kind 0 only).  Each stored value
-// is loaded once and meets the NR right-hand sides of its x row in NR fused multiply-adds, so the matrix is
-// streamed once per NR columns.  A slot still folds its stripe serially in stored row order and every
-// column j keeps an accumulator of its own, so column j of Y is, bit for bit, what spmv_slots gives for
-// column j of X.  A launch covers nr <= NR live columns starting at the X / Y pointers it is given; columns
-// j >= nr are neither read nor written.
-//   VEC (chosen by the host per launch, nr == NR only): the X row and the Y row of a lane are moved with 8- /
-//       16-B vector accesses (X, Y and both leading dimensions aligned to the vector); otherwise element by
-//       element, the column index clamped to nr - 1 on loads so they stay unconditional.
+// One body (run_slots_mm, and run_slots_narrow_mm for the fp32 w = 2 two-segment rows) serves both operand layouts;
+// the layout is a compile-time parameter (RhsLayout) that decides only how a lane fetches the NR right-hand sides
+// of a stored row and how it writes its outputs.  The kernels read the SlotBin arena of spmv_slots -- no layout of
+// their own -- and keep run_slots's lane -> (slot, sub) map, chunks, ranges, PAD / LAST handling, clamped
+// unconditional loads, two-stage ping-pong and `live` select (kind 0 only).  Each stored value is loaded once and
+// meets the NR right-hand sides of its x row in NR fused multiply-adds, so the matrix is streamed once per NR
+// columns.  A slot still folds its stripe serially in stored row order and every column j keeps an accumulator of
+// its own, so column j of Y is, bit for bit, what spmv_slots gives for column j of X.  A launch covers nr <= NR
+// live columns starting at the X / Y pointers it is given; columns j >= nr are neither read nor written.
+//   Row-major (spmm_slots; kRhsRows, kRhsRowsVec): X (m x nrhs) and Y (n x nrhs) with the right-hand sides
+//       interleaved, X[i * ldx + j].  A lane moves its X row and its Y row with ld_rhs / st_rhs: with 8- / 16-B
+//       vector accesses under kRhsRowsVec (chosen by the host per launch, nr == NR only: X, Y and both leading
+//       dimensions aligned to the vector), otherwise element by element, the column index clamped to nr - 1 on
+//       loads so they stay unconditional.
+//   Column-major (spmm_slots_col; kRhsCols): X[i + j * ldx], Y[i + j * ldy] with ldx >= m, ldy >= n (a Julia
+//       Matrix), the operand addressing of run_slots per column.
+//       gather: NR element loads x[gi + j * ldx] per stored row, the column index clamped to nr - 1 so the loads
+//           stay unconditional (the column bases are wave-uniform: one vector offset serves the NR loads).
+//       flush:  per live column the lane writes its V contiguous outputs at y + j * ldy + o + sub * V with
+//           run_slots's direct-flush forms -- one 8- / 16-B store when the lane owns its whole vector, element
+//           stores under e < lim otherwise; q = alpha * acc, then fmadd(beta, y, q) only when beta != 0.
 //   y offsets: affine, or table-mapped and staged through LDS per range (kSlotOutEntries, as run_slots).
 //   The staged-burst write path of spmv_slots (NB > 0) has no counterpart here.
 #pragma once
 #include "vbc_slots.h"
 
 namespace vbc {
+
+// The operand layout of an instance: row-major element by element, row-major with vector moves, column-major.
+enum RhsLayout { kRhsRows, kRhsRowsVec, kRhsCols };
 
 // One row of NR right-hand sides: p[0 .. nr).
 template <typename T, int NR, bool VEC>
@@ -68,7 +81,7 @@ __device__ __forceinline__ void st_rhs(gptr<T> p, int nr, const T (&a)[NR], T al
     }
 }
 
-template <typename T, int W_, int U, bool KC, typename S, int NR, bool VEC>
+template <typename T, int W_, int U, bool KC, typename S, int NR, RhsLayout LAY>
 __device__ __forceinline__ void run_slots_mm(const SlotBin &b, int r, int lane, const T *__restrict__ x, int64_t ldx,
                                              T *__restrict__ y, int64_t ldy, int nr, T alpha, T beta, bool rd,
                                              int *lds_out)
@@ -84,7 +97,15 @@ __device__ __forceinline__ void run_slots_mm(const SlotBin &b, int r, int lane, 
     const int lslot = active ? slot : 0, lsub = active ? sub : 0;
     const gptr<const S> val = G(static_cast<const S *>(b.val));
     const gptr<const uint32_t> key = G(b.key);
-    const gptr<const T> xg = G(x);
+    constexpr bool COL = LAY == kRhsCols, VEC = LAY == kRhsRowsVec;
+    // column-major: the columns of X a launch reads, base j of a dead column (j >= nr) being the last live column's
+    gptr<const T> xc[COL ? NR : 1];
+    if constexpr (COL) {
+#pragma unroll
+        for (int j = 0; j < NR; j++) xc[j] = G(x) + (int64_t)min(j, nr - 1) * ldx;
+    } else {
+        xc[0] = G(x);
+    }
 
     // Loads are unconditional (rows past the range re-read its last row and are never folded), as in run_slots.
     typedef __attribute__((address_space(4))) const uint32_t *cptr;  // scalar (constant) loads
@@ -110,7 +131,12 @@ __device__ __forceinline__ void run_slots_mm(const SlotBin &b, int r, int lane, 
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t gi = KC ? (bs[u] & kSlotIdx) + (kk[u] == kPad16 ? 0u : kk[u]) : kk[u] & kSlotIdx;
-            ld_rhs<T, NR, VEC>(xg + (size_t)gi * ldx, nr, xv[u]);
+            if constexpr (COL) {
+#pragma unroll
+                for (int j = 0; j < NR; j++) xv[u][j] = xc[j][gi];
+            } else {
+                ld_rhs<T, NR, VEC>(xc[0] + (size_t)gi * ldx, nr, xv[u]);
+            }
         }
     };
     T acc[NR][V];
@@ -130,13 +156,39 @@ __device__ __forceinline__ void run_slots_mm(const SlotBin &b, int r, int lane, 
         if (active && seg < b.nseg) {
             const int o = b.out_affine ? b.out_base + seg * b.out_stride : lds_out[(c - c0) * RPI + slot];
             const int lim = b.wst - sub * V;  // padding columns (w > wst) are never written
+            if constexpr (COL) {
 #pragma unroll
-            for (int e = 0; e < V; e++) {
-                if (e < lim) {
-                    T a[NR];
+                for (int j = 0; j < NR; j++) {
+                    if (j < nr) {
+                        gptr<T> yo = G(y) + (int64_t)j * ldy + o + sub * V;
+                        T q[V];
 #pragma unroll
-                    for (int j = 0; j < NR; j++) a[j] = acc[j][e];
-                    st_rhs<T, NR, VEC>(G(y) + (size_t)(o + sub * V + e) * ldy, nr, a, alpha, beta, rd);
+                        for (int e = 0; e < V; e++) {
+                            q[e] = alpha * acc[j][e];
+                            if (rd && e < lim) q[e] = fmadd(beta, yo[e], q[e]);
+                        }
+                        if (V > 1 && lim >= V) {  // the lane's whole vector: one 8- / 16-B store
+                            typedef T vt __attribute__((ext_vector_type(V)));
+                            vt t;
+#pragma unroll
+                            for (int e = 0; e < V; e++) t[e] = q[e];
+                            *(gptr<vt>)yo = t;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < V; e++)
+                                if (e < lim) yo[e] = q[e];
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; e++) {
+                    if (e < lim) {
+                        T a[NR];
+#pragma unroll
+                        for (int j = 0; j < NR; j++) a[j] = acc[j][e];
+                        st_rhs<T, NR, VEC>(G(y) + (size_t)(o + sub * V + e) * ldy, nr, a, alpha, beta, rd);
+                    }
                 }
             }
         }
@@ -188,7 +240,7 @@ __device__ __forceinline__ void run_slots_mm(const SlotBin &b, int r, int lane, 
 
 // The narrow rows of run_slots_narrow (fp32 w = 2: one lane holds two consecutive segments, 128 slots per
 // chunk, a row's values one 16-B load per lane and its keys one 4- / 8-B load).
-template <int U, bool KC, int NR, bool VEC>
+template <int U, bool KC, int NR, RhsLayout LAY>
 __device__ __forceinline__ void run_slots_narrow_mm(const SlotBin &b, int r, int lane, const float *__restrict__ x,
                                                     int64_t ldx, float *__restrict__ y, int64_t ldy, int nr,
                                                     float alpha, float beta, bool rd, int *lds_out)
@@ -200,7 +252,14 @@ __device__ __forceinline__ void run_slots_narrow_mm(const SlotBin &b, int r, int
     if (R0 >= R1) return;
     int c = G(b.rchunk)[r];
     const gptr<const T> val = G(static_cast<const T *>(b.val));
-    const gptr<const T> xg = G(x);
+    constexpr bool COL = LAY == kRhsCols, VEC = LAY == kRhsRowsVec;
+    gptr<const T> xc[COL ? NR : 1];
+    if constexpr (COL) {
+#pragma unroll
+        for (int j = 0; j < NR; j++) xc[j] = G(x) + (int64_t)min(j, nr - 1) * ldx;
+    } else {
+        xc[0] = G(x);
+    }
     typedef __attribute__((address_space(4))) const uint32_t *cptr;
     const cptr bases = (cptr)b.base;
     const cptr doffs = (cptr)b.kdoff;
@@ -236,7 +295,12 @@ __device__ __forceinline__ void run_slots_narrow_mm(const SlotBin &b, int r, int
 #pragma unroll
             for (int k = 0; k < SPL; k++) {
                 const uint32_t gi = KC ? (bs[u] & kSlotIdx) + (kk[u][k] == kPad16 ? 0u : kk[u][k]) : kk[u][k] & kSlotIdx;
-                ld_rhs<T, NR, VEC>(xg + (size_t)gi * ldx, nr, xv[u][k]);
+                if constexpr (COL) {
+#pragma unroll
+                    for (int j = 0; j < NR; j++) xv[u][k][j] = xc[j][gi];
+                } else {
+                    ld_rhs<T, NR, VEC>(xc[0] + (size_t)gi * ldx, nr, xv[u][k]);
+                }
             }
     };
     T acc[NR][NV];
@@ -256,13 +320,40 @@ __device__ __forceinline__ void run_slots_narrow_mm(const SlotBin &b, int r, int
             const int seg = seg0 + k;
             if (seg < b.nseg) {
                 const int o = b.out_affine ? b.out_base + seg * b.out_stride : lds_out[(c - c0) * RPI + lane * SPL + k];
+                if constexpr (COL) {
+                    const int lim = b.wst;
 #pragma unroll
-                for (int e = 0; e < W_; e++) {
-                    if (e < b.wst) {
-                        T a[NR];
+                    for (int j = 0; j < NR; j++) {
+                        if (j < nr) {
+                            gptr<T> yo = G(y) + (int64_t)j * ldy + o;
+                            T q[W_];
 #pragma unroll
-                        for (int j = 0; j < NR; j++) a[j] = acc[j][k * W_ + e];
-                        st_rhs<T, NR, VEC>(G(y) + (size_t)(o + e) * ldy, nr, a, alpha, beta, rd);
+                            for (int e = 0; e < W_; e++) {
+                                q[e] = alpha * acc[j][k * W_ + e];
+                                if (rd && e < lim) q[e] = fmadd(beta, yo[e], q[e]);
+                            }
+                            if (lim >= W_) {  // the segment's whole width: one 8-B store
+                                typedef T st __attribute__((ext_vector_type(W_)));
+                                st t;
+#pragma unroll
+                                for (int e = 0; e < W_; e++) t[e] = q[e];
+                                *(gptr<st>)yo = t;
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < W_; e++)
+                                    if (e < lim) yo[e] = q[e];
+                            }
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < W_; e++) {
+                        if (e < b.wst) {
+                            T a[NR];
+#pragma unroll
+                            for (int j = 0; j < NR; j++) a[j] = acc[j][k * W_ + e];
+                            st_rhs<T, NR, VEC>(G(y) + (size_t)(o + e) * ldy, nr, a, alpha, beta, rd);
+                        }
                     }
                 }
             }
@@ -324,11 +415,9 @@ __host__ __device__ constexpr int slot_mm_step(int NR)
 
 // One wave per range, bins and XCD-aware block order as spmv_slots.  WONLY = 2 / kWonlyNarrow2: every bin of the
 // launch has width 2 in the plain / the narrow-row form (the FE width), so only that case is compiled.
-template <typename T, bool KC, typename S, int NR, bool VEC, int WONLY = -1>
-__global__ __launch_bounds__(kBlockThreads) void spmm_slots(const SlotBin *__restrict__ bins, int nbins,
-                                                            int total_ranges, int xcd_chunk, const T *__restrict__ x,
-                                                            int64_t ldx, T *__restrict__ y, int64_t ldy, int nr,
-                                                            T alpha, T beta, int rd_i)
+template <typename T, bool KC, typename S, int NR, RhsLayout LAY, int WONLY>
+__device__ __forceinline__ void slots_mm_wave(const SlotBin *bins, int nbins, int total_ranges, int xcd_chunk, const T *x,
+                                              int64_t ldx, T *y, int64_t ldy, int nr, T alpha, T beta, int rd_i)
 {
     int blk = blockIdx.x;
     if (xcd_chunk > 0) blk = xcd_block(blk, gridDim.x);
@@ -343,15 +432,15 @@ __global__ __launch_bounds__(kBlockThreads) void spmm_slots(const SlotBin *__res
     __shared__ int outs[kWavesPerBlock * kSlotOutEntries];
     int *lds_out = outs + (threadIdx.x >> 6) * kSlotOutEntries;
     constexpr int U = slot_mm_step<T, KC>(NR);
-#define VBC_MM_W(W) run_slots_mm<T, W, slot_step<T>(W, U), KC, S, NR, VEC>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out)
+#define VBC_MM_W(W) run_slots_mm<T, W, slot_step<T>(W, U), KC, S, NR, LAY>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out)
     if constexpr (WONLY == 2) {
         VBC_MM_W(2);
     } else if constexpr (WONLY == kWonlyNarrow2) {
-        run_slots_narrow_mm<U / 2, KC, NR, VEC>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out);
+        run_slots_narrow_mm<U / 2, KC, NR, LAY>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out);
     } else {
         if constexpr (sizeof(T) == 4 && sizeof(S) == 4) {
             if (b.spl == 2 && b.wkey == 2) {
-                run_slots_narrow_mm<U / 2, KC, NR, VEC>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out);
+                run_slots_narrow_mm<U / 2, KC, NR, LAY>(b, r, lane, x, ldx, y, ldy, nr, alpha, beta, rd, lds_out);
                 return;
             }
         }
@@ -368,6 +457,29 @@ __global__ __launch_bounds__(kBlockThreads) void spmm_slots(const SlotBin *__res
         }
     }
 #undef VBC_MM_W
+}
+
+// Row-major operands; VEC: kRhsRowsVec.
+template <typename T, bool KC, typename S, int NR, bool VEC, int WONLY = -1>
+__global__ __launch_bounds__(kBlockThreads) void spmm_slots(const SlotBin *__restrict__ bins, int nbins,
+                                                            int total_ranges, int xcd_chunk, const T *__restrict__ x,
+                                                            int64_t ldx, T *__restrict__ y, int64_t ldy, int nr,
+                                                            T alpha, T beta, int rd_i)
+{
+    slots_mm_wave<T, KC, S, NR, VEC ? kRhsRowsVec : kRhsRows, WONLY>(bins, nbins, total_ranges, xcd_chunk, x, ldx, y, ldy,
+                                                                     nr, alpha, beta, rd_i);
+}
+
+// Column-major operands.
+template <typename T, bool KC, typename S, int NR, int WONLY = -1>
+__global__ __launch_bounds__(kBlockThreads) void spmm_slots_col(const SlotBin *__restrict__ bins, int nbins,
+                                                                int total_ranges, int xcd_chunk,
+                                                                const T *__restrict__ x, int64_t ldx,
+                                                                T *__restrict__ y, int64_t ldy, int nr, T alpha,
+                                                                T beta, int rd_i)
+{
+    slots_mm_wave<T, KC, S, NR, kRhsCols, WONLY>(bins, nbins, total_ranges, xcd_chunk, x, ldx, y, ldy, nr, alpha, beta,
+                                                 rd_i);
 }
 
 }  // namespace vbc

@@ -1,6 +1,7 @@
 // spmm_slots launchers for one value type (included by vbc_slots_mm_f64.hip / vbc_slots_mm_f32.hip /
-// vbc_slots_mm_f64n.hip, which define VBC_SLOTS_T and VBC_SLOTS_SUFFIX, and VBC_SLOTS_S when the stored values
-// are narrower than VBC_SLOTS_T): one translation unit per type so they compile in parallel.
+// vbc_slots_mm_f64n.hip) and, with VBC_SLOTS_COL defined, spmm_slots_col launchers (vbc_slots_mmc_*.hip).  The unit
+// defines VBC_SLOTS_T and VBC_SLOTS_SUFFIX, and VBC_SLOTS_S when the stored values are narrower than VBC_SLOTS_T: one
+// translation unit per operand layout and type so they compile in parallel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,6 +20,10 @@ static void launch_mm_t(const SlotBin *d_bins, int nbins, int total_ranges, int 
 {
     const int grid = (total_ranges + kWavesPerBlock - 1) / kWavesPerBlock;
     const int xcd_chunk = (xcd && grid >= 16) ? 1 : 0;
+#ifdef VBC_SLOTS_COL
+    hipLaunchKernelGGL((spmm_slots_col<T, KC, S, NR, WONLY>), dim3(grid), dim3(kBlockThreads), 0, s, d_bins, nbins,
+                       total_ranges, xcd_chunk, x, ldx, y, ldy, nr, (T)alpha, (T)beta, (int)rd);
+#else
     // vector moves of a lane's X / Y row: every live column, both bases and both row pitches on the vector's bytes
     constexpr uintptr_t kVecBytes = NR * sizeof(T) >= 16 ? 16 : NR * sizeof(T);
     const bool vec = nr == NR && ((uintptr_t)x | (uintptr_t)y | (uintptr_t)(ldx * (int64_t)sizeof(T)) |
@@ -29,15 +34,22 @@ static void launch_mm_t(const SlotBin *d_bins, int nbins, int total_ranges, int 
     else
         hipLaunchKernelGGL((spmm_slots<T, KC, S, NR, false, WONLY>), dim3(grid), dim3(kBlockThreads), 0, s, d_bins, nbins,
                            total_ranges, xcd_chunk, x, ldx, y, ldy, nr, (T)alpha, (T)beta, (int)rd);
+#endif
 }
 
 #define VBC_CAT2(a, b) a##b
 #define VBC_CAT(a, b) VBC_CAT2(a, b)
 
-// nr <= 8 live columns at x / y.  wonly: 2 or kWonlyNarrow2 when every bin of the launch has that form, else -1.
-int VBC_CAT(launch_slots_mm_, VBC_SLOTS_SUFFIX)(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc,
-                                                int wonly, const void *x, int64_t ldx, void *y, int64_t ldy, int nr,
-                                                double alpha, double beta, bool rd, hipStream_t stream)
+#ifdef VBC_SLOTS_COL
+#define VBC_SLOTS_ENTRY VBC_CAT(launch_slots_mmc_, VBC_SLOTS_SUFFIX)
+#else
+#define VBC_SLOTS_ENTRY VBC_CAT(launch_slots_mm_, VBC_SLOTS_SUFFIX)
+#endif
+
+// The slotted bins of a launch (total_ranges > 0), nr <= 8 live columns at x / y (row pitches, or column strides,
+// ldx / ldy).  wonly: 2 or kWonlyNarrow2 when every bin of the launch has that form, else -1.
+int VBC_SLOTS_ENTRY(const SlotBin *d_bins, int nbins, int total_ranges, int xcd, bool kc, int wonly, const void *x,
+                    int64_t ldx, void *y, int64_t ldy, int nr, double alpha, double beta, bool rd, hipStream_t stream)
 {
     typedef VBC_SLOTS_T T;
     typedef VBC_SLOTS_S S;

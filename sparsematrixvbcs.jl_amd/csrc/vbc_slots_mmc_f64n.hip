@@ -2,4 +2,5 @@
 #define VBC_SLOTS_T double
 #define VBC_SLOTS_S float
 #define VBC_SLOTS_SUFFIX f64n
-#include "vbc_slots_mmc_launch.inc"
+#define VBC_SLOTS_COL
+#include "vbc_slots_mm_launch.inc"

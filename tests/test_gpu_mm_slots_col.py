@@ -1,4 +1,4 @@
-"""Column-major multi-RHS B'X fused over the slotted layout (spmm_slots_col, csrc/vbc_slots_mmc.h; vbc.h planar_mask
+"""Column-major multi-RHS B'X fused over the slotted layout (spmm_slots_col, csrc/vbc_slots_mm.h; vbc.h planar_mask
 bit 23).
 
 The operands are what a Julia Matrix is: X[i + j * ldx], Y[i + j * ldy].  A slot folds its stripe serially in stored
