@@ -219,7 +219,7 @@ struct SweepBin {
 };
 constexpr int kSweepTileBytes = 8192;  // LDS accumulators per wave: VBC_SWEEP_TILE = 8 / 16 / 32 (KB)
 
-// Launches spmv_sweep (vbc_sweep.hip): returns the hipError_t of the launch.
+// Launches spmv_sweep (vbc_sweep.hip, vbc_sweep_f64n.hip; the launchers are vbc_sweep_launch.inc): returns the hipError_t of the launch.
 // vsz: size of the stored values (esz, or 4 on an fp64 launch whose bins all keep Float32 values).
 int launch_sweep(int esz, int vsz, int kind, const SweepBin *d_bins, int nbins, int total_tiles, int tile_bytes, int diag,
                  const void *x, void *y, double alpha, double beta, bool rd, hipStream_t stream);
@@ -230,10 +230,11 @@ constexpr int kWonlyNarrow2 = 102;  // spmv_slots WONLY: fp32 B'x w = 2 folded t
 int launch_slots(int esz, int vsz, int kind, const SlotBin *d_bins, int nbins, int total_ranges, bool faste, int xcd, int u, int diag, int stage, bool kc,
                  int wonly, const void *x, void *y, double alpha, double beta, bool rd, hipStream_t stream);
 int occupancy_slots(int esz, int kind);
-// vbc_planar.hip; a bin with vsz = 4 goes to the kernels of vbc_planar_f64n.hip (fp64 on Float32 stored values) or,
-// where there is none for its layout, fails with hipErrorInvalidValue
-int launch_planar(int esz, const SlotBin &hb, const SlotBin *d_b, bool faste, bool staged, const void *x, void *y,
-                  double alpha, double beta, bool rd, hipStream_t s);
+// Launches the kernel of one planar bin (vbc_planar.hip picks the unit by value type: vbc_planar_f64.hip,
+// vbc_planar_f32.hip, or vbc_planar_f64n.hip -- fp64 on Float32 stored values -- for a bin with vsz = 4); a form
+// without a kernel fails with hipErrorInvalidValue
+int launch_planar(int esz, const SlotBin &hb, bool faste, bool staged, const void *x, void *y, double alpha, double beta,
+                  bool rd, hipStream_t s);
 int occupancy_planar(int esz);
 int occupancy_split_multi(int esz, int P);
 int launch_split_multi(int esz, const SplitMulti &M, int P, const void *x, void *y, double alpha, double beta, bool rd,

@@ -97,8 +97,8 @@ static int launch_group(const Launch &L, int kind, const void *x, void *y, doubl
         if (!mine(true)) continue;
         const bool faste = !rd && pb.out_affine && !ablation_knob("VBC_NO_FASTE");
         const bool staged = faste && pb.contig && slot_stage != 0;
-        const hipError_t e = (hipError_t)launch_planar((int)sizeof(T), pb, L.d_pbins + i, faste, staged, x, y, alpha,
-                                                       beta, rd, stream);
+        const hipError_t e = (hipError_t)launch_planar((int)sizeof(T), pb, faste, staged, x, y, alpha, beta, rd,
+                                                       stream);
         if (e != hipSuccess) {
             set_error("spmv_planar launch failed: %s", hipGetErrorString(e));
             return VBC_HIP_ERROR;

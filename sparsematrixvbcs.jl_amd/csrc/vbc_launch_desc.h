@@ -25,7 +25,7 @@ struct Launch {
     SlotBin *d_sbins = nullptr;
     int slot_ranges = 0;
     std::vector<SlotBin> pbins;    // planar slotted buckets (vbc_planar.h), one launch each
-    SlotBin *d_pbins = nullptr;
+    SlotBin *d_pbins = nullptr;  // (uploaded, but no kernel reads it: the planar kernels take their bin by value)
     std::vector<SweepBin> wbins;   // row-swept buckets (vbc_sweep.hip, B'x only), launched first
     SweepBin *d_wbins = nullptr;
     int sweep_tiles = 0;

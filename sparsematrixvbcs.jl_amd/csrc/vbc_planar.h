@@ -1,5 +1,5 @@
 // gfx950 planar slotted kernel for mul!(y, B', x) with stripes 3..8 columns wide (device code,
-// included by vbc_planar.hip only).
+// included through vbc_planar_launch.inc by the vbc_planar_f64 / _f32 / _f64n.hip units, and by vbc_planar_mmc.h).
 //
 // The slotted layout of vbc_slots.h gives a segment (stripe) LPR = w / V lanes when a stored row is
 // wider than one 16-B lane vector: fp64 w = 3 runs 3 lanes per stripe with 8-B loads, 21 stripes per

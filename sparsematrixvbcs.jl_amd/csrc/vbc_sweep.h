@@ -16,8 +16,8 @@
 // in L2 and each x line comes from HBM / MALL about once per XCD instead of once per gather.
 // After its last step the wave writes y for its stripes once (alpha, beta applied there).
 //
-// The kernel templates: vbc_sweep.hip instantiates them on values of the compute eltype, vbc_sweep_f64n.hip on
-// Float32 values under fp64 compute (VBC_CREATE_NARROW_SWEPT).
+// The kernel templates: the launchers of vbc_sweep_launch.inc instantiate them, in vbc_sweep.hip on values of the
+// compute eltype, in vbc_sweep_f64n.hip on Float32 values under fp64 compute (VBC_CREATE_NARROW_SWEPT).
 #pragma once
 #include <hip/hip_runtime.h>
 

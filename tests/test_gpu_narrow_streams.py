@@ -108,7 +108,7 @@ def run_case(knobs, env, B, trans, run, seed, R=None, targets=("1", "8", "256"),
 def test_bx_widths_runs_tiles(knobs, w, run):
     """spmv_planar_lanes<double, w, run, false, RD, 0, float>, both RD (the two (alpha, beta) of AB): 170 ragged
     stripes over m = 300 as one or two tiles, tiles of a few dozen stripes and tiles of 4.  (The DEEP form is instantiated as
-    launch_lanes_w has it, but VBC_LANES_DEEP is a tuning knob the product library does not read: no product test
+    launch_stream (vbc_planar_launch.inc) has it, but VBC_LANES_DEEP is a tuning knob the product library does not read: no product test
     can launch it, for the wide kernel as for this one.)"""
     run_case(knobs, LANES, ragged(w, run, stripes=170), True, run, seed=70 + w)
 
